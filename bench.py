@@ -6,6 +6,17 @@
 and exits with their status; under torchrun (the driver's launch) it checks WORLD_SIZE == N.
 Rank 0 prints ONE JSON line.
 
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps,
+print the line (`value`, `ms_per_step`, the configuration, and `kernel_ms`: the library's own HIP
+events over the timed steps, which cost no run of their own).  `--full` adds everything else to the
+same line: `roofline` and `hbm_frac_step` (byte-counting passes over the outputs), `end_to_end`
+(runs of its own) and `cpu_baseline` (the oracle on the CPU); `--no-end-to-end` /
+`--no-cpu-baseline` drop those two legs from a full run.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step decoded -- a fixed, seeded
+sample of the records of every batch, every output column -- as DIR/<name>.npy (dump_outputs below).
+The inputs are seeded, so two builds run with the same arguments can be compared file by file.
+
 Shards, weak scaling -- the per-GPU work is fixed as N grows:
   fixed-length (C2, C3): rank r decodes records [r n, (r + 1) n) of an N n-record job; the
       Record_Id base r n is static, there is no collective on the data path;
@@ -848,6 +859,142 @@ def _cpu_baseline(workload: str, seconds: float = 10.0):
 
 
 # ------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # hard limit of a dump
+DUMP_BUDGET_BYTES = DUMP_LIMIT_BYTES // 2   # what the sample is sized for (strings counted at 64 bytes a value)
+DUMP_SEED = 20261019
+
+
+def dump_column_name(ci: int, info) -> str:
+    """c<column>_<field>: the copybook field's name, or the column's kind for a generated one."""
+    import re
+    label = info.node.name if info.node is not None else info.kind
+    return "c%03d_%s" % (ci, re.sub(r"[^A-Za-z0-9]+", "_", label))
+
+
+def _dump_part(plan, cols, n_rec: int, idx, save) -> None:
+    """The decoded values of records idx (sorted indices into a batch of n_rec records) of every
+    column, gathered on the device: save(name, tensor) per array."""
+    import torch
+    from cobrix_amd import native as N
+    dev = cols[0]["validity"].device
+    di = torch.as_tensor(idx, dtype=torch.int64, device=dev).view(1, -1)
+    pitch = 64 * ((n_rec + 63) // 64)
+    lo32 = 0xFFFFFFFF
+
+    def bits(bitmap, pos):   # the bits at positions pos of a bitmap packed into int64 words
+        return ((bitmap[pos // 64] >> (pos % 64)) & 1).bool()
+
+    for ci, info in enumerate(plan.columns):
+        if info.kind == "list_offsets":   # where a record's list elements lie: layout, read through below
+            continue
+        c = cols[ci]
+        name = dump_column_name(ci, info)
+        rows = torch.arange(info.n_slots, dtype=torch.int64, device=dev).view(-1, 1)
+        ot = info.out_type
+        if info.list_array >= 0 and ot not in (N.O_STRING, N.O_BINARY):
+            # list layout: element j of a record at child index offsets[record] + j, j < count[record]
+            ar = plan.arrays[info.list_array]
+            cc = cols[ar.count_column]
+            cnt = cc["values"][di].to(torch.int64) * bits(cc["validity"], di)
+            present = rows < cnt
+            pos = torch.where(present, cols[ar.offsets_column]["values"][di].to(torch.int64) + rows, 0)
+            pos = pos.clamp(0, c["values"].numel() // (2 if ot == N.O_DEC128 else 1) - 1)
+            valid = present & bits(c["validity"], pos)
+        else:
+            pos = rows * pitch + di    # slot-major rows of `pitch` values; the bitmaps likewise
+            valid = bits(c["validity"], pos)
+        save(name + ".valid", valid.to(torch.float32))
+        if ot in (N.O_STRING, N.O_BINARY):
+            data = c["data"]
+            if "views" in c:   # 16-byte views: length, then <= 12 bytes inline or prefix + buffer + offset
+                v = c["views"].view(-1, 16)[pos]
+                w = v.view(torch.int32).view(info.n_slots, -1, 4)
+                ln = w[..., 0].to(torch.int64) * valid
+                start = rows * c["capacity"] + w[..., 2].to(torch.int64) * max(1, c["buffer_bytes"]) + w[..., 3]
+            elif "offsets32" in c:   # Utf8: int32 offsets relative to the slot's region
+                o = c["offsets32"].view(info.n_slots, pitch + 1).to(torch.int64)
+                start = o[rows, di] + rows * c["capacity"]
+                ln = (o[rows, di + 1] - o[rows, di]) * valid
+            else:               # large-string: int64 offsets into the column's data
+                o = c["offsets"].view(info.n_slots, pitch + 1)
+                start = o[rows, di]
+                ln = (o[rows, di + 1] - o[rows, di]) * valid
+            width = max(1, int(ln.max().item()))
+            j = torch.arange(width, dtype=torch.int64, device=dev)
+            text = data[(start.unsqueeze(-1) + j).clamp(0, data.numel() - 1)]
+            if "views" in c:
+                inline = torch.zeros(v.shape[:-1] + (max(width, 12),), dtype=torch.uint8, device=dev)
+                inline[..., :12] = v[..., 4:16]
+                text = torch.where((ln > 12).unsqueeze(-1), text, inline[..., :width])
+            text = text * (j < ln.unsqueeze(-1))
+            save(name + ".length", ln.to(torch.float32))
+            save(name + ".bytes", text.to(torch.float32))
+            continue
+        vals = c["values"]
+        if ot == N.O_DEC128:    # two int64 words a value (low, high) -> 32-bit words, most significant first
+            g = vals.view(-1, 2)[pos] * valid.unsqueeze(-1)
+            out = torch.stack([g[..., 1] >> 32, g[..., 1] & lo32, g[..., 0] >> 32, g[..., 0] & lo32], -1)
+        elif ot in (N.O_I64, N.O_DEC64):   # exact in float64 as (high word, signed; low word)
+            g = vals[pos] * valid
+            out = torch.stack([g >> 32, g & lo32], -1)
+        elif ot == N.O_F32:
+            out = (vals[pos] * valid).view(torch.float32)
+        elif ot == N.O_F64:
+            out = (vals[pos] * valid).view(torch.float64)
+        else:
+            out = vals[pos] * valid
+        save(name + ".values", out.to(torch.float32 if ot == N.O_F32 else torch.float64))
+
+
+def dump_outputs(job, out_dir: str, rank: int, world: int) -> dict:
+    """--dump-outputs: what the last timed step left in the job's output columns, for a fixed sample
+    of records (seeded; sorted; the same for the same arguments) of every batch, as .npy files:
+
+      [rank<r>_][batch<b>_]records.npy                 the sampled record indices within the batch
+      [..]c<column>_<field>.valid.npy     [slots, records] 1 = a value, 0 = null (or past the list's end)
+      [..]c<column>_<field>.values.npy    [slots, records(, words)] nulls as 0: int32 / float / double as
+                                          themselves; int64 and decimals as exact 32-bit words, most
+                                          significant (signed) first: 2 words, 4 for decimals > 18 digits
+      [..]c<column>_<field>.length.npy    [slots, records] UTF-8 bytes of a string value
+      [..]c<column>_<field>.bytes.npy     [slots, records, longest] the bytes, zero-padded
+
+    float64 for .values (float32 for float columns), float32 otherwise.  OCCURS DEPENDING ON lists are
+    read through their offsets: slot j = element j of the record's list."""
+    import numpy as np
+    import torch
+    from cobrix_amd import native as N
+    os.makedirs(out_dir, exist_ok=True)
+    plan = job.rd.plan
+    per_rec = 8   # bytes a sampled record takes
+    for info in plan.columns:
+        if info.kind != "list_offsets":
+            wide = 4 * 64 + 4 if info.out_type in (N.O_STRING, N.O_BINARY) else 2 * N.OUT_WIDTH[info.out_type]
+            per_rec += info.n_slots * (4 + wide)
+    written = {"files": 0, "bytes": 0}
+    torch.cuda.synchronize()
+    for b, (_, m, cols, _) in enumerate(job.parts):
+        if m <= 0:
+            continue
+        k = max(1, min(m, DUMP_BUDGET_BYTES // (per_rec * len(job.parts))))
+        idx = np.sort(np.random.default_rng(DUMP_SEED + b).choice(m, size=k, replace=False))
+        prefix = (f"rank{rank}_" if world > 1 else "") + (f"batch{b}_" if len(job.parts) > 1 else "")
+
+        def save(name, t):
+            a = t.cpu().numpy()
+            written["files"] += 1
+            written["bytes"] += a.nbytes
+            if written["bytes"] > DUMP_LIMIT_BYTES:
+                raise RuntimeError(f"--dump-outputs: more than {DUMP_LIMIT_BYTES} bytes at {name}")
+            np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+        save("records", torch.as_tensor(idx, dtype=torch.float64))
+        _dump_part(plan, cols, m, idx, save)
+    return written
+
+
+# ------------------------------------------------------------------------------------------------
 # launcher
 # ------------------------------------------------------------------------------------------------
 def _free_port() -> int:
@@ -931,14 +1078,22 @@ def main():
                     help="OCCURS DEPENDING ON layout: Arrow lists (present elements) or one slot row per element")
     ap.add_argument("--seed-mb", type=int, default=100, choices=[100, 32],
                     help="var-len index entry size: 100 MB default (reset) or a 32 MB block size (subtracted)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report roofline / hbm_frac_step (byte counts of the outputs), end_to_end (pinned host "
+                         "-> HBM passes) and cpu_baseline (the oracle on the CPU); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write a fixed seeded sample of what the last step decoded as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the cpu_baseline leg out")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: leave the end_to_end leg out")
     ap.add_argument("--dry-run", action="store_true", help="CPU plumbing only (gloo): launcher, all-gather, timing")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (RCCL, the measured path) or gloo: ranks may then share one GPU and collectives "
                          "go through host copies -- a correctness run of the multi-rank path on a one-GPU box, "
                          "not a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1029,7 +1184,13 @@ def main():
     if world > 1:
         _all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    # the async framing of a var-len step decodes over the count the index run predicts: the step
+    # is only the step if the framing found that count (and the Record_Id base is the prefix)
     check = job.verify(world)
+    if args.dump_outputs:
+        progress(f"writing outputs to {args.dump_outputs}")
+        wrote = dump_outputs(job, args.dump_outputs, rank, world)
+        progress(f"{wrote['files']} files, {wrote['bytes'] / 1e6:.1f} MB")
 
     n_rec = job.n_rec
     plan = job.rd.plan
@@ -1042,40 +1203,9 @@ def main():
     ms_per_step = elapsed / steps * 1e3
     gbs = job_bytes / (elapsed / steps) / 1e9
     recs_per_s = job_recs / (elapsed / steps)
-    # per batch (a fixed-length job decodes its shard in batches; the others in one call), summed
     parts = getattr(job, "parts", None) or [(0, n_rec, job.cols, None)]
-    alg = lay = absent = 0
-    has_lists = any(c.list_array >= 0 for c in plan.columns)
-    for i, (_, m, cols, _) in enumerate(parts):
-        present = present_elements(plan, cols, m)
-        payload = string_payload(plan, cols, m)
-        in_b = job.part_bytes(i) if hasattr(job, "part_bytes") else m * job.stride if len(parts) > 1 else job.in_bytes
-        alg += algorithmic_bytes(plan, m, in_b, payload, present)
-        lay += layout_bytes(plan, cols, m, in_b, payload, present)
-        # OCCURS lists: the 8(d) input term counts every record byte, absent ODO elements included;
-        # the bytes the kernels must move leave those out (reported beside, never as `frac`)
-        absent += absent_element_bytes(plan, cols, m) if has_lists else 0
     dec_avg_ms = sum(dec[: nc.value]) / max(1, args.steps)     # per step: every call of the step
     fix_avg_ms = sum(fix[: nc.value]) / max(1, args.steps)
-    # the decode chain: the record kernel (+ its Utf8 count pass and scan, list kernels) and the fixup
-    # pass of the values it deferred -- all of cbx_decode_*'s device work
-    chain_ms = dec_avg_ms + fix_avg_ms
-    piped = hasattr(job, "pipelined") and job.pipelined()
-    if piped:   # two plans' chains overlap on two streams: the step's wall time is the chain
-        chain_ms = ms_per_step
-    achieved = alg / (chain_ms * 1e-3) / 1e9
-    kind = ctypes.c_int32(0)
-    N.check(L.cbx_plan_kernel_kind(h, ctypes.byref(kind)))
-    kname = {1: "cbx_jit_decode (copybook-specialised, hipRTC)", 2: "cbx::walk_kernel (record walk)"}.get(
-        kind.value, "cbx::decode_kernel (table-driven)")
-    if strings == "offsets" and any(c.out_type in (N.O_STRING, N.O_BINARY) for c in plan.columns):
-        kname = "Utf8 count pass (cbx_jit_count) + device scan + " + kname + " (decode_kernel time covers all three)"
-    lists = any(c.list_array >= 0 for c in plan.columns)
-    if lists:   # the OCCURS list elements: the element-parallel kernel launched right after the decode kernel
-        kname += " + cbx::list_kernel (OCCURS lists; decode_kernel time covers both)"
-    kname += " + cbx::fixup_kernel (deferred values; post_kernels time)"
-    tag = f"{args.workload}_{strings}{'' if args.occurs == 'lists' else '_slots'}_{n_rec}"
-    traffic, traffic_src = measured_traffic(tag)
     kernel_ms = {"decode_kernel": round(dec_avg_ms, 4), "post_kernels": round(fix_avg_ms, 4)}
     fms = None
     if frame_ev:
@@ -1084,19 +1214,67 @@ def main():
     if hasattr(job, "index_ms"):
         kernel_ms["sparse_index_setup (untimed, once: frame + cbx_sparse_index of the whole file, or of this "
                   "rank's block + tail in the N > 1 chain)"] = round(job.index_ms, 3)
-    e2e = None
-    if not args.no_end_to_end and world == 1:
-        progress("end-to-end (pinned host -> HBM) pass")
-        e2e = job.end_to_end()
-    progress("cpu baseline" if not args.no_cpu_baseline and world == 1 else "done")
     kernels_sum = dec_avg_ms + fix_avg_ms + (fms or 0.0)
+    roofline = hbm_frac_step = e2e = None
+    if args.full:
+        # per batch (a fixed-length job decodes its shard in batches; the others in one call), summed
+        alg = lay = absent = 0
+        has_lists = any(c.list_array >= 0 for c in plan.columns)
+        for i, (_, m, cols, _) in enumerate(parts):
+            present = present_elements(plan, cols, m)
+            payload = string_payload(plan, cols, m)
+            in_b = job.part_bytes(i) if hasattr(job, "part_bytes") else m * job.stride if len(parts) > 1 else job.in_bytes
+            alg += algorithmic_bytes(plan, m, in_b, payload, present)
+            lay += layout_bytes(plan, cols, m, in_b, payload, present)
+            # OCCURS lists: the 8(d) input term counts every record byte, absent ODO elements included;
+            # the bytes the kernels must move leave those out (reported beside, never as `frac`)
+            absent += absent_element_bytes(plan, cols, m) if has_lists else 0
+        # the decode chain: the record kernel (+ its Utf8 count pass and scan, list kernels) and the fixup
+        # pass of the values it deferred -- all of cbx_decode_*'s device work
+        chain_ms = dec_avg_ms + fix_avg_ms
+        piped = hasattr(job, "pipelined") and job.pipelined()
+        if piped:   # two plans' chains overlap on two streams: the step's wall time is the chain
+            chain_ms = ms_per_step
+        achieved = alg / (chain_ms * 1e-3) / 1e9
+        kind = ctypes.c_int32(0)
+        N.check(L.cbx_plan_kernel_kind(h, ctypes.byref(kind)))
+        kname = {1: "cbx_jit_decode (copybook-specialised, hipRTC)", 2: "cbx::walk_kernel (record walk)"}.get(
+            kind.value, "cbx::decode_kernel (table-driven)")
+        if strings == "offsets" and any(c.out_type in (N.O_STRING, N.O_BINARY) for c in plan.columns):
+            kname = "Utf8 count pass (cbx_jit_count) + device scan + " + kname + " (decode_kernel time covers all three)"
+        if has_lists:   # the OCCURS list elements: the element-parallel kernel launched right after the decode kernel
+            kname += " + cbx::list_kernel (OCCURS lists; decode_kernel time covers both)"
+        kname += " + cbx::fixup_kernel (deferred values; post_kernels time)"
+        tag = f"{args.workload}_{strings}{'' if args.occurs == 'lists' else '_slots'}_{n_rec}"
+        traffic, traffic_src = measured_traffic(tag)
+        hbm_frac_step = round(alg / (elapsed / steps) / 1e9 / HBM_PEAK_GBS, 4)
+        roofline = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "frac_of_measured_peak": round(achieved / HBM_MEASURED_GBS, 4),
+                    "algorithmic_bytes_per_launch": alg,
+                    **({"absent_element_bytes": absent, "moved_bytes_per_launch": alg - absent,
+                        "frac_moved_bytes": round((alg - absent) / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                        "note": "8(d) counts the input records whole (absent ODO elements included); "
+                                "frac_moved_bytes counts what the kernels must read and write"}
+                       if absent else {}),
+                    "layout_bytes_per_launch": lay, "layout_overhead": lay - alg,
+                    "timing": ("wall time of the step: two plans' count + decode chains overlapped on two streams "
+                               "(cbx_plan_pipeline)") if piped else
+                              ("HIP events on the launch stream (cbx_plan_kernel_times): decode_kernel + post_kernels "
+                               "(the fixup pass), average of the timed steps"),
+                    "traffic": traffic, "traffic_source": traffic_src}
+        if not args.no_end_to_end and world == 1:
+            progress("end-to-end (pinned host -> HBM) pass")
+            e2e = job.end_to_end()
+    cpu_leg = args.full and not args.no_cpu_baseline and world == 1
+    progress("cpu baseline" if cpu_leg else "done")
     if rank == 0:
         out = {
             "metric": METRIC,
             "value": round(gbs, 3),
             "unit": "GB/s",
             "records_per_s": round(recs_per_s, 1),
-            "hbm_frac_step": round(alg / (elapsed / steps) / 1e9 / HBM_PEAK_GBS, 4),
+            **({"hbm_frac_step": hbm_frac_step} if args.full else {}),
             "n_gpus": world,
             "steps": steps,
             "warmup": args.warmup,
@@ -1122,25 +1300,11 @@ def main():
             "step_vs_kernels": round(ms_per_step / kernels_sum, 3) if kernels_sum > 0 else None,
             **({"seeds": f"{len(job.seeds)} sparse-index entries of this rank's run ({args.seed_mb} MB, root segments)",
                 "record_id_check": check} if hasattr(job, "seeds") else {}),
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "frac_of_measured_peak": round(achieved / HBM_MEASURED_GBS, 4),
-                         "algorithmic_bytes_per_launch": alg,
-                         **({"absent_element_bytes": absent, "moved_bytes_per_launch": alg - absent,
-                             "frac_moved_bytes": round((alg - absent) / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                             "note": "8(d) counts the input records whole (absent ODO elements included); "
-                                     "frac_moved_bytes counts what the kernels must read and write"}
-                            if absent else {}),
-                         "layout_bytes_per_launch": lay, "layout_overhead": lay - alg,
-                         "timing": ("wall time of the step: two plans' count + decode chains overlapped on two streams "
-                                    "(cbx_plan_pipeline)") if piped else
-                                   ("HIP events on the launch stream (cbx_plan_kernel_times): decode_kernel + post_kernels "
-                                    "(the fixup pass), average of the timed steps"),
-                         "traffic": traffic, "traffic_source": traffic_src},
+            **({"roofline": roofline} if args.full else {}),
         }
         if e2e is not None:
             out["end_to_end"] = e2e
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_leg:
             out["cpu_baseline"] = _cpu_baseline(args.workload)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -18,7 +18,7 @@ for rep in 1 2; do
     for V in "${VS[@]}"; do
       if [ "$V" = "-" ]; then unset CBX_LIB_VARIANT; else export CBX_LIB_VARIANT=$V; fi
       F=$OUT/${NAME}_${V/-/prod}_$rep
-      timeout -k 10 400 python -u bench.py --workload $W $EXTRA --steps 8 --warmup 2 --no-cpu-baseline --no-end-to-end > $F.json 2> $F.err || { tail -8 $F.err; exit 1; }
+      timeout -k 10 400 python -u bench.py --workload $W $EXTRA --steps 8 --warmup 2 --full --no-cpu-baseline --no-end-to-end > $F.json 2> $F.err || { tail -8 $F.err; exit 1; }
       python3 -c "import json; d=json.load(open('$F.json')); print('$NAME', '$V', $rep, d['ms_per_step'], d.get('kernel_ms'), d['roofline']['frac'])"
     done
   done

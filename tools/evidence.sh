@@ -21,7 +21,7 @@ for SPEC in "$@"; do
   W=${SPEC%%:*}; EXTRA=""; NAME=$W
   if [ "$SPEC" != "$W" ]; then EXTRA=$(echo ${SPEC#*:} | tr ',' ' '); NAME=${W}$(echo ${SPEC#*:} | tr -d '-' | tr ', ' '__'); fi
   D=$OUT/$NAME; mkdir -p $D
-  timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -o run -- python3 -u bench.py --workload $W $EXTRA --steps 10 --warmup 3 > $D/bench.json 2> $D/bench.err
+  timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -o run -- python3 -u bench.py --workload $W $EXTRA --steps 10 --warmup 3 --full > $D/bench.json 2> $D/bench.err
   rc=$?; cat $D/bench.json
   [ $rc -eq 0 ] || { echo "bench $NAME failed rc=$rc"; tail -20 $D/bench.err; exit 1; }
   i=0

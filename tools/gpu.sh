@@ -30,14 +30,14 @@ fi
 spec() { W=${1%%:*}; EXTRA=""; NAME=$W; if [ "$1" != "$W" ]; then EXTRA=$(echo ${1#*:} | tr ',' ' '); NAME=${W}$(echo ${1#*:} | tr -d '-' | tr ', ' '__'); fi; }
 for S in ${BENCH:-}; do
   spec "$S"
-  timeout -k 10 400 python -u bench.py --workload $W $EXTRA --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end > $OUT/b_$NAME.json 2> $OUT/b_$NAME.err || { tail -8 $OUT/b_$NAME.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --workload $W $EXTRA --steps 5 --warmup 2 --full --no-cpu-baseline --no-end-to-end > $OUT/b_$NAME.json 2> $OUT/b_$NAME.err || { tail -8 $OUT/b_$NAME.err; exit 1; }
   python3 -c "import json; d=json.load(open('$OUT/b_$NAME.json')); print('$NAME', d['ms_per_step'], d.get('kernel_ms'), d['roofline']['frac'])"
 done
 cd /tmp && export TMPDIR=/tmp
 for S in ${PROF:-}; do
   spec "$S"
   D=$OUT/p_$NAME; mkdir -p $D
-  timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -o run -- python3 -u $ROOTDIR/bench.py --workload $W $EXTRA --steps 10 --warmup 3 --no-cpu-baseline --no-end-to-end > $D/bench.json 2> $D/bench.err
+  timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -o run -- python3 -u $ROOTDIR/bench.py --workload $W $EXTRA --steps 10 --warmup 3 --full --no-cpu-baseline --no-end-to-end > $D/bench.json 2> $D/bench.err
   rc=$?; [ $rc -eq 0 ] || { echo "prof $NAME failed rc=$rc"; tail -8 $D/bench.err; exit 1; }
   python3 -c "import json; d=json.load(open('$D/bench.json')); print('$NAME', d['ms_per_step'], d.get('kernel_ms'), d['roofline']['frac'])"
   f=$(find $D/trace -name "*kernel_stats.csv" | head -1); head -8 $f | cut -d, -f1-5
