@@ -26,6 +26,7 @@
 #include "cbx_hier.h"
 #include "cbx_walk.h"
 #include "cbx_chain.h"
+#include "cbx_filter.h"
 
 using namespace cbx;
 
@@ -164,6 +165,7 @@ struct cbx_plan {
     std::vector<hipEvent_t> ev_pool;     // free events
     struct CallEvents { hipEvent_t e[3]; };
     std::vector<CallEvents> ev_calls;    // recorded, not yet read
+    float flt_ms[3] = {0.f, 0.f, 0.f};   // test / scan / emit of the last cbx_filter_records call (profiling)
 };
 
 #include "cbx_jit.h"
@@ -2166,6 +2168,104 @@ extern "C" int cbx_decode_selected(cbx_plan* P, const uint8_t* d_data, int64_t n
             HIP_CHECK(hipMemcpyAsync(col.data_sizes, offs64 + n_rec, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         HIP_CHECK(hipGetLastError());
     }
+    return CBX_OK;
+}
+
+// Row filter in front of the decode (cbx_filter.h): test -> scan of the tile counts -> emit.
+extern "C" int cbx_filter_records(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                  const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                  int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                                  cbx_selection* out, int64_t* n_selected, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !filter || !out || !n_selected || n_rec < 0 || n_bytes < 0 || start_offset < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records: invalid arguments");
+    *n_selected = 0;
+    P->flt_ms[0] = P->flt_ms[1] = P->flt_ms[2] = 0.f;
+    const int n_src =(in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records: exactly one source (selection, framed records, record stride)");
+    const int L = P->opts.has_segments ? P->opts.segments.n_levels : 0;
+    if (!in && L > 0)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records: a plan with Seg_Id levels filters a selection (cbx_select_records)");
+    std::vector<FilterProg> prog(1);
+    std::string err;
+    const int rb = filter_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, filter, prog.data(), err);
+    if (rb != CBX_OK) return fail(rb, err);
+    if (in) out->file_id = in->file_id;   // (an empty selection carries the batch's File_Id too)
+    if (n_rec == 0) return CBX_OK;
+    if (!d_data || !out->rec_off || !out->rec_len || !out->record_id || !out->segment ||
+        (in && (!in->rec_off || !in->rec_len || !in->record_id || !in->segment)) ||
+        (in && L > 0 && (!in->seg_state || !out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records: selection arrays required");
+    if (in && (in->rec_off == out->rec_off || in->rec_len == out->rec_len || in->record_id == out->record_id ||
+               in->segment == out->segment || (L > 0 && in->seg_state == out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records: out must not share arrays with in");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records: n_rec records of rec_stride bytes exceed n_bytes");
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    const int64_t nb = scan_sums_len(n_tiles + 1);
+    // block: program | keep words (n_tiles) | base (n_tiles + 1) | sums (nb) | counts (n_tiles + 1) | segments (n_rec)
+    const size_t o_keep = (sizeof(FilterProg) + 15) & ~(size_t)15;
+    const size_t o_base = o_keep + sizeof(uint64_t) * n_tiles;
+    const size_t o_sums = o_base + sizeof(int64_t) * (n_tiles + 1);
+    const size_t o_cnt = o_sums + sizeof(int64_t) * nb;
+    AsyncBlock blk(st);
+    const size_t o_seg = o_cnt + sizeof(uint32_t) * (n_tiles + 2);
+    const bool map_seg = !in && P->opts.has_segments;   // the active segment comes from the plan's segment map
+    HIP_CHECK(hipMallocAsync(&blk.p, o_seg + (map_seg ? sizeof(int16_t) * (size_t)n_rec : 0) + 16, st));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    int64_t* base = (int64_t*)(b8 + o_base);
+    int64_t* sums = (int64_t*)(b8 + o_sums);
+    uint32_t* counts = (uint32_t*)(b8 + o_cnt);
+    HIP_CHECK(hipMemcpyAsync(b8, prog.data(), sizeof(FilterProg), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(counts + n_tiles, 0, sizeof(uint32_t), st));
+    FilterArgs a{};
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = (const CBX_CONST FilterProg*)b8;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    a.keep = (uint64_t*)(b8 + o_keep);
+    a.counts = counts;
+    a.seg_out = map_seg ? (int16_t*)(b8 + o_seg) : nullptr;
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    hipEvent_t* ev = pe.e;
+    if (P->profiling) {
+        for (int k = 0; k < 4; k++) if (!(ev[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    const unsigned grid = blocks_for(n_tiles, kFltThreads / kWave);
+    hipLaunchKernelGGL(filter_test_kernel, dim3(grid), dim3(kFltThreads), 0, st, a);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    device_scan(counts, n_tiles + 1, base, sums, st);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+    cbx_selection none{};
+    hipLaunchKernelGGL(filter_emit_kernel, dim3(grid), dim3(kFltThreads), 0, st, a, (const int64_t*)base, in ? *in : none,
+                       in ? 1 : 0, L > 0 ? 1 + L : 0, first_record_id, *out);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[3], st));
+    HIP_CHECK(hipGetLastError());
+    int64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, base + n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (P->profiling)
+        for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&P->flt_ms[k], ev[k], ev[k + 1]));
+    *n_selected = total;
+    return CBX_OK;
+}
+
+extern "C" int cbx_filter_pass_times(cbx_plan* P, float* test_ms, float* scan_ms, float* emit_ms) {
+    if (!P) return fail(CBX_E_ARGUMENT, "null plan");
+    if (test_ms) *test_ms = P->flt_ms[0];
+    if (scan_ms) *scan_ms = P->flt_ms[1];
+    if (emit_ms) *emit_ms = P->flt_ms[2];
     return CBX_OK;
 }
 

@@ -43,8 +43,9 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_sparse_index", "cbx_select_records", "cbx_decode_selected", "cbx_hier_select",
                     "cbx_hier_list_offsets", "cbx_plan_set_walk", "cbx_frame_var_occurs",
                     "cbx_plan_set_record_base", "cbx_frame_length_field", "cbx_plan_set_odo_counts",
-                    "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline")
-ABI_VERSION = 20
+                    "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline",
+                    "cbx_filter_records", "cbx_filter_pass_times")
+ABI_VERSION = 21
 
 
 class NativeLibraryError(RuntimeError):
@@ -123,6 +124,33 @@ class CbxSelection(ctypes.Structure):
     _fields_ = [("rec_off", ctypes.c_void_p), ("rec_len", ctypes.c_void_p), ("record_id", ctypes.c_void_p),
                 ("segment", ctypes.c_void_p), ("seg_state", ctypes.c_void_p), ("file_id", ctypes.c_int32),
                 ("footer_bytes", ctypes.c_int32)]
+
+
+# row filters (cbx_filter): ops, table limits
+(OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_IN, OP_NOT_IN, OP_IS_NULL, OP_IS_NOT_NULL, OP_STARTS_WITH,
+ OP_NOT_STARTS_WITH) = range(1, 13)
+CBX_FILTER_MAX_TERMS, CBX_FILTER_MAX_LITERALS, CBX_FILTER_POOL_BYTES = 32, 64, 1024
+# the filter stage keeps one count per tile of 64 records and scans them in blocks of kScanTile counts
+# (cbx_kernels.hip: kScanBlock * kScanItems): a batch past FILTER_SCAN_BLOCK_RECORDS takes a second scan block
+FILTER_TILE_RECORDS = 64
+FILTER_SCAN_BLOCK_RECORDS = 256 * 8 * FILTER_TILE_RECORDS
+
+
+class CbxFilterLiteral(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64), ("str_off", ctypes.c_int32),
+                ("str_len", ctypes.c_int32)]
+
+
+class CbxFilterTerm(ctypes.Structure):
+    _fields_ = [("field", ctypes.c_int32), ("op", ctypes.c_int32), ("group", ctypes.c_int32),
+                ("lit_begin", ctypes.c_int32), ("lit_count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class CbxFilter(ctypes.Structure):
+    _fields_ = [("n_terms", ctypes.c_int32), ("n_literals", ctypes.c_int32), ("pool_bytes", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("terms", CbxFilterTerm * CBX_FILTER_MAX_TERMS),
+                ("literals", CbxFilterLiteral * CBX_FILTER_MAX_LITERALS),
+                ("pool", ctypes.c_uint8 * CBX_FILTER_POOL_BYTES)]
 
 
 W_GROUP, W_PRIM = 0, 1
@@ -228,7 +256,9 @@ def load():
                      ("cbx_hier_dependee_values", [P, P, i64, P, P, i64, i32, i32, P, P, P]),
                      ("cbx_plan_set_dep_seed", [P, P, i64, i32]),
                      ("cbx_views_to_utf8", [P, i64, P, i64, P, P, i64, P, P]),
-                     ("cbx_plan_pipeline", [P, P, i32, i32])):
+                     ("cbx_plan_pipeline", [P, P, i32, i32]),
+                     ("cbx_filter_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, P]),
+                     ("cbx_filter_pass_times", [P, P, P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import copybook as cbk
 from . import native as N
+from .filter import compile_filters
 from .plan import DecodePlan, NativePlan, NeedsWalk, build_plan
 from .schema import ST_DECIMAL, spark_schema
 
@@ -120,6 +121,9 @@ class DecodedBatch:
         self.generate_record_id = generate_record_id
         # with_input_file_name_col: (column name, the file's name) -- a per-batch constant column
         self.input_file: Optional[Tuple[str, str]] = None
+        # filters= of the read that produced the batch: those the GPU stage did not evaluate
+        # (PrunedFilteredScan.unhandledFilters); the caller applies them to the rows
+        self.unhandled_filters: List[Any] = []
 
     def generated(self, column, r=None) -> List[Tuple[str, Any]]:
         """The generated leading fields of the rows: (schema name, value) pairs, value = column(ci)
@@ -910,6 +914,47 @@ class _BaseReader:
             views_to_utf8(self.plan, cols, n_rec, stream)
         return DecodedBatch(self.plan, n_rec, cols, first_record_id, self.collapse_root, gen_id)
 
+    def _empty_selection(self, n: int, device) -> Tuple[Dict[str, Any], N.CbxSelection]:
+        """Device arrays of a cbx_selection holding up to n rows."""
+        torch = _torch()
+        nl = self.plan.options.segments.n_levels if self.plan.options.has_segments else 0
+        sel = {"rec_off": torch.empty(max(1, n), dtype=torch.int64, device=device),
+               "rec_len": torch.empty(max(1, n), dtype=torch.int32, device=device),
+               "record_id": torch.empty(max(1, n), dtype=torch.int64, device=device),
+               "segment": torch.empty(max(1, n), dtype=torch.int32, device=device),
+               "seg_state": torch.empty(max(1, n * (1 + nl)), dtype=torch.int64, device=device)}
+        cs = N.CbxSelection()
+        for k in ("rec_off", "rec_len", "record_id", "segment", "seg_state"):
+            setattr(cs, k, sel[k].data_ptr())
+        return sel, cs
+
+    def _filter_records(self, table, d_data, n_bytes: int, n_rec: int, st, *, sel=None, rec_off=None, rec_len=None,
+                        stride: int = 0, first_record_id: int = 0, file_id: int = 0) -> Dict[str, Any]:
+        """cbx_filter_records over one source (a selection, framed records, fixed-length records): the
+        surviving rows as a selection for cbx_decode_selected."""
+        out, cs = self._empty_selection(n_rec, d_data.device)
+        cs.file_id = sel["struct"].file_id if sel is not None else file_id
+        ns = ctypes.c_int64(0)
+        N.check(N.load().cbx_filter_records(
+            self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+            rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+            n_rec, stride, self.params.start_offset, first_record_id, ctypes.byref(table), ctypes.byref(cs),
+            ctypes.byref(ns), ctypes.c_void_p(st.cuda_stream)))
+        out["n"] = ns.value
+        out["struct"] = cs
+        out["source"] = sel   # (the input selection's arrays stay alive with the result)
+        return out
+
+    def _decode_selection(self, d_data, n_bytes: int, sel: Dict[str, Any], gen_id: bool, st) -> DecodedBatch:
+        """cbx_decode_selected into column buffers sized by the selection's row count."""
+        n_rec = sel["n"]
+        cols, cs = _alloc_columns(self.plan, n_rec, string_capacity(self.native, n_rec), d_data.device)
+        L = N.load()
+        N.check(L.cbx_decode_selected(self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]),
+                                      n_rec, self.params.start_offset, cs, ctypes.c_void_p(st.cuda_stream)))
+        N.check(L.cbx_plan_check(self.native.handle, ctypes.c_void_p(st.cuda_stream)))
+        return self._batch(n_rec, cols, 0, gen_id, st)
+
     def close(self):
         peer = getattr(self, "_peer", None)
         if peer is not None:   # (the pipelined second plan of decode_batches)
@@ -957,17 +1002,33 @@ class FixedLenNestedReader(_BaseReader):
                 raise ValueError(f"Binary record size {exp} does not divide data size {n_bytes}.")
 
     def decode_device(self, d_data, n_bytes: int, first_record_id: int = 0, stream=None,
-                      exact_strings: bool = False) -> DecodedBatch:
+                      exact_strings: bool = False, filters=None) -> DecodedBatch:
         """Decode a split already resident in HBM (d_data: uint8 CUDA tensor).
 
         One asynchronous kernel launch; string payloads go to regions sized by the upper bound
         (or by the exact pre-pass when exact_strings=True).  cbx_plan_check synchronises and
-        raises if a payload overflowed."""
+        raises if a payload overflowed.
+        filters: `cobrix_amd.filter` filters (AND-ed, PrunedFilteredScan.buildScan): the rows they keep are
+        selected on the GPU before the decode (cbx_filter_records -> cbx_decode_selected) and the column
+        buffers sized by their count; `batch.unhandled_filters` lists the filters left to the caller.
+        exact_strings does not apply to a filtered read: its string regions are sized by the upper bound
+        for the surviving rows (the exact pre-pass runs over whole batches only)."""
         torch = _torch()
         stride = self.get_record_size()
         n_rec = n_bytes // stride
         st = stream if stream is not None else torch.cuda.current_stream()
         L = N.load()
+        if filters:
+            table, unhandled = compile_filters(self.plan, filters)
+            if table is not None:
+                sel = self._filter_records(table, d_data, n_bytes, n_rec, st, stride=stride,
+                                           first_record_id=first_record_id)
+                batch = self._decode_selection(d_data, n_bytes, sel, False, st)
+                batch.unhandled_filters = unhandled
+                return batch
+            batch = self.decode_device(d_data, n_bytes, first_record_id, stream, exact_strings)
+            batch.unhandled_filters = unhandled
+            return batch
         exact = None
         if exact_strings:
             sizes = (ctypes.c_int64 * self.plan.n_columns)()
@@ -1021,11 +1082,11 @@ class FixedLenNestedReader(_BaseReader):
             s0.wait_stream(targets[1][1])
         return [self._batch(m, cols, fid, False, st) for m, cols, fid, st in out]
 
-    def decode(self, data: bytes, first_record_id: int = 0) -> DecodedBatch:
+    def decode(self, data: bytes, first_record_id: int = 0, filters=None) -> DecodedBatch:
         torch = _torch()
         self.check_binary_data_validity(len(data))
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
-        return self.decode_device(t, len(data), first_record_id)
+        return self.decode_device(t, len(data), first_record_id, filters=filters)
 
     def get_row_iterator(self, data: bytes) -> Iterator[dict]:
         return iter(self.decode(data).to_rows())
@@ -1247,13 +1308,41 @@ class VarLenNestedReader(_BaseReader):
     def decode_selected(self, d_data, n_bytes: int, sel: Dict[str, Any], stream=None) -> DecodedBatch:
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream()
-        n_rec = sel["n"]
-        cols, cs = _alloc_columns(self.plan, n_rec, string_capacity(self.native, n_rec), d_data.device)
-        L = N.load()
-        N.check(L.cbx_decode_selected(self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]),
-                                      n_rec, self.params.start_offset, cs, ctypes.c_void_p(st.cuda_stream)))
-        N.check(L.cbx_plan_check(self.native.handle, ctypes.c_void_p(st.cuda_stream)))
-        return self._batch(n_rec, cols, 0, self.params.generate_record_id, st)
+        batch = self._decode_selection(d_data, n_bytes, sel, self.params.generate_record_id, st)
+        batch.unhandled_filters = sel.get("unhandled", [])
+        return batch
+
+    def filter(self, d_data, n_bytes: int, sel_or_framing, filters, first_record_id: int = 0, file_id: int = 0,
+               stream=None) -> Dict[str, Any]:
+        """The rows `filters` keep (cobrix_amd.filter, AND-ed), selected on the GPU: of a selection (`select`'s
+        result: record ids, segments and Seg_Id state carried over) or of framed records ((rec_off, rec_len):
+        Record_Id = first_record_id + index).  Returns a selection for `decode_selected`; its "unhandled" entry
+        lists the filters left to the caller (they are not applied).
+        A reader with segment id levels (Seg_IdN columns) filters a selection only: the Seg_Id state is
+        accumulated by `select`, so framed records are refused (CBX_E_ARGUMENT) -- call `select` first."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "filters on a hierarchical read: dropping rows would break the tree")
+        table, unhandled = compile_filters(self.plan, filters)
+        is_sel = isinstance(sel_or_framing, dict)
+        if not is_sel and self.plan.seg_id_columns:
+            raise N.CbxError(N.CBX_E_ARGUMENT, "filter: a reader with segment id levels filters a selection "
+                                               "(the Seg_IdN state comes from select()); pass select()'s result")
+        if table is None:
+            if is_sel:
+                out = dict(sel_or_framing)
+            else:   # no filter to evaluate: every framed record, as a selection
+                table = N.CbxFilter()
+        if table is not None:
+            if is_sel:
+                out = self._filter_records(table, d_data, n_bytes, sel_or_framing["n"], st, sel=sel_or_framing)
+            else:
+                rec_off, rec_len = sel_or_framing
+                out = self._filter_records(table, d_data, n_bytes, int(rec_off.numel()), st, rec_off=rec_off,
+                                           rec_len=rec_len, first_record_id=first_record_id, file_id=file_id)
+        out["unhandled"] = unhandled
+        return out
 
     def decode_device(self, d_data, n_bytes: int, rec_off, rec_len, first_record_id: int = 0,
                       stream=None, exact_strings: bool = False) -> DecodedBatch:
@@ -1280,7 +1369,7 @@ class VarLenNestedReader(_BaseReader):
         return self._batch(n_rec, cols, first_record_id, self.params.generate_record_id, st)
 
     def read_entries(self, d_data, n_bytes: int, entries: Sequence[SparseIndexEntry], entries_per_piece: int = 1,
-                     file_id: int = 0, input_file_name: Optional[str] = None) -> List[DecodedBatch]:
+                     file_id: int = 0, input_file_name: Optional[str] = None, filters=None) -> List[DecodedBatch]:
         """An RDW file as the reference reads it -- a partition per sparse-index entry
         (CobolScanners.buildScanForVarLenIndex, SC/source/scanners/CobolScanners.scala:40-75), each with
         its own VarLenNestedIterator from the entry's offset and record index -- `entries_per_piece`
@@ -1288,7 +1377,7 @@ class VarLenNestedReader(_BaseReader):
         seeded at them, cbx_frame_rdw), then selected and decoded, one piece after another on the
         current stream (framing returns the piece's record count to the host, so pieces do not
         overlap).  The batches, in file order, hold the rows `read` returns.
-        input_file_name: as in `read`."""
+        input_file_name, filters: as in `read`."""
         torch = _torch()
         self._file_column(None, input_file_name, check_only=True)
         if not self.params.is_record_sequence or self.params.is_text or self.hierarchical:
@@ -1324,6 +1413,8 @@ class VarLenNestedReader(_BaseReader):
             rebased = [SparseIndexEntry(e.offset_from - a, e.offset_to - a if e.offset_to >= 0 else -1, e.file_id,
                                         e.record_index) for e in group]
             sel = self.select(piece, b - a, off[: n.value], ln[: n.value], rebased, file_id, stream=main)
+            if filters:
+                sel = self.filter(piece, b - a, sel, filters, stream=main)
             out.append(self._file_column(self.decode_selected(piece, b - a, sel, stream=main), input_file_name))
         return out
 
@@ -1674,11 +1765,15 @@ class VarLenNestedReader(_BaseReader):
         seeds._cbx_keep = (vals, valid)
         return seeds
 
-    def read(self, data: bytes, file_id: int = 0, input_file_name: Optional[str] = None) -> DecodedBatch:
+    def read(self, data: bytes, file_id: int = 0, input_file_name: Optional[str] = None, filters=None) -> DecodedBatch:
         """A whole file, as the reference reads it: sparse-index entries (when index generation
         applies) each read by its own VarLenNestedIterator, concatenated in file order.
-        input_file_name: the file's name for the with_input_file_name_col column."""
+        input_file_name: the file's name for the with_input_file_name_col column.
+        filters: cobrix_amd.filter filters (AND-ed), applied on the GPU after `select` and before the decode;
+        `batch.unhandled_filters` lists those left to the caller."""
         self._file_column(None, input_file_name, check_only=True)
+        if filters and self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "filters on a hierarchical read: dropping rows would break the tree")
         t = self._device_file(data)
         off, ln, vb = self.frame_file(t, len(data))
         if self.hierarchical:
@@ -1687,13 +1782,30 @@ class VarLenNestedReader(_BaseReader):
         if self.index_generation_needed() and not self.params.is_text:
             entries = self.generate_index(t, len(data), off, ln, file_id)
         sel = self.select(t, vb, off, ln, entries, file_id)
+        if filters:
+            sel = self.filter(t, vb, sel, filters)
         return self._file_column(self.decode_selected(t, vb, sel), input_file_name)
 
     def decode(self, data: bytes, seeds: Optional[Sequence[int]] = None, first_record_id: int = 0,
-               input_file_name: Optional[str] = None) -> DecodedBatch:
-        """Frame + decode as one entry (no selection stage).  input_file_name: as in `read`."""
+               input_file_name: Optional[str] = None, filters=None) -> DecodedBatch:
+        """Frame + decode as one entry (no selection stage).  input_file_name, filters: as in `read` (the
+        filter stage then takes the framed records: Record_Id = first_record_id + record index; a reader
+        with segment id levels has no Seg_Id state without the selection stage and raises CBX_E_ARGUMENT
+        for filters here -- use `read`)."""
         self._file_column(None, input_file_name, check_only=True)
         t = self._device_file(data)
+        if filters:
+            if self.hierarchical:
+                raise N.CbxError(N.CBX_E_UNSUPPORTED, "filters on a hierarchical read: dropping rows would break the tree")
+            unseeded = self.params.is_text or self.var_occurs_extractor() or (
+                self.params.record_length_field is not None and not self.params.is_record_sequence)
+            if unseeded:
+                off, ln, vb = self.frame_file(t, len(data))
+            else:
+                off, ln = self.frame(t, len(data), seeds) if self.params.is_record_sequence else self.frame_fixed(t, len(data))
+                vb = len(data)
+            sel = self.filter(t, vb, (off, ln), filters, first_record_id=first_record_id)
+            return self._file_column(self.decode_selected(t, vb, sel), input_file_name)
         if self.params.is_text or self.var_occurs_extractor() or (
                 self.params.record_length_field is not None and not self.params.is_record_sequence):
             # framings that are not seeded by RDW headers: text lines, VarOccursRecordExtractor,

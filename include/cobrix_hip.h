@@ -43,7 +43,7 @@ typedef __hip_internal::uint64_t uint64_t;
 extern "C" {
 #endif
 
-#define CBX_ABI_VERSION 20
+#define CBX_ABI_VERSION 21
 
 /* status codes */
 #define CBX_OK 0
@@ -417,6 +417,76 @@ int cbx_select_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, c
  * (SegmentIdAccumulator.getSegmentLevelId: prefix_fileId_rootRecordId[_L<level>_<counter>]). */
 int cbx_decode_selected(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* sel,
                         int64_t n_rec, int32_t start_offset, cbx_column* columns, void* stream);
+
+/* ---- row filters pushed down to the GPU ----
+ *
+ * What Spark's PrunedFilteredScan.buildScan(requiredColumns, filters) hands a relation, evaluated before
+ * the decode so that only surviving records are decoded and written (the reference filters rows after
+ * RecordExtractors.extractRecord, on a lazy iterator).  cbx_filter is a predicate table in conjunctive
+ * normal form: terms of one `group` are OR-ed, groups are AND-ed; terms are listed with non-decreasing
+ * group; an empty table keeps every record.  A term compares one field of the plan's cbx_field table
+ * with its literals [lit_begin, lit_begin + lit_count).
+ * SQL three-valued logic: a comparison with a null value is unknown, a record is kept only when the
+ * whole filter is true.  A field is null exactly where the decode makes it null: a malformed value, a
+ * numeric reaching past the record's end, a field of a segment redefine that is not the record's
+ * active segment (and a string starting past the record's end); a string cut by a short record
+ * compares as the truncated value.  Negated comparisons are ops of their own (no NOT node: under
+ * three-valued logic NOT(a < b) and a >= b keep the same rows).
+ * Numerics compare as the column's output value (int32 / int64 / the unscaled decimal at the Spark
+ * scale, 128-bit signed for precision > 18) with literals given as 128-bit two's complement at that
+ * scale; strings compare as the decoded UTF-8 bytes (code page, trimming) in unsigned byte order
+ * (UTF8String.compareTo) with literals held in `pool`. */
+#define CBX_FILTER_MAX_TERMS 32
+#define CBX_FILTER_MAX_LITERALS 64
+#define CBX_FILTER_POOL_BYTES 1024
+enum cbx_filter_op {
+    CBX_OP_EQ = 1, CBX_OP_NE = 2, CBX_OP_LT = 3, CBX_OP_LE = 4, CBX_OP_GT = 5, CBX_OP_GE = 6,
+    CBX_OP_IN = 7, CBX_OP_NOT_IN = 8,              /* any / none of lit_count literals equal */
+    CBX_OP_IS_NULL = 9, CBX_OP_IS_NOT_NULL = 10,   /* no literal */
+    CBX_OP_STARTS_WITH = 11, CBX_OP_NOT_STARTS_WITH = 12   /* strings, one literal */
+};
+typedef struct {
+    uint64_t lo, hi;       /* numeric fields: two's complement 128-bit value at the field's output scale */
+    int32_t str_off;       /* string fields: UTF-8 bytes pool[str_off, str_off + str_len) */
+    int32_t str_len;
+} cbx_filter_literal;
+typedef struct {
+    int32_t field;         /* index into the plan's cbx_field table */
+    int32_t op;            /* cbx_filter_op */
+    int32_t group;         /* terms of one group are OR-ed, groups AND-ed */
+    int32_t lit_begin, lit_count;
+    int32_t reserved;
+} cbx_filter_term;
+typedef struct {
+    int32_t n_terms, n_literals, pool_bytes, reserved;
+    cbx_filter_term terms[CBX_FILTER_MAX_TERMS];
+    cbx_filter_literal literals[CBX_FILTER_MAX_LITERALS];
+    uint8_t pool[CBX_FILTER_POOL_BYTES];
+} cbx_filter;
+
+/* The records of one source that `filter` keeps, in source order, as a selection cbx_decode_selected
+ * takes.  Sources (exactly one):
+ *   in != NULL:          the n_rec rows of a selection (cbx_select_records): record ids, active segment
+ *                        and seg_state are carried over;
+ *   d_rec_off/d_rec_len: framed records (payload offsets / lengths);
+ *   rec_stride > 0:      fixed-length records, record i at d_data + i * rec_stride.
+ * For the last two Record_Id = first_record_id + i and the active segment comes from the plan's segment
+ * map as cbx_select_records takes it (-1 without one); a plan with Seg_Id levels needs a selection.
+ * out's arrays (capacity n_rec each, distinct from in's) receive the kept rows; *n_selected their count
+ * (one host wait).  Three passes on `stream`: test (one lane per record: the terms' fields are decoded
+ * from the record's bytes, a keep bit per record and a count per 64 records stored), scan of the
+ * counts, emit.
+ * CBX_E_UNSUPPORTED (reason in cbx_last_error): a field inside an OCCURS; a record-walk plan
+ * (data-dependent offsets); a comparison on COMP-1 / COMP-2 (IS_NULL / IS_NOT_NULL are fine); UTF-16,
+ * HEX and RAW fields; generated columns.  CBX_E_ARGUMENT: a malformed table. */
+int cbx_filter_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                       const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                       int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                       cbx_selection* out, int64_t* n_selected, void* stream);
+
+/* Durations in ms of the three passes of the plan's last cbx_filter_records call, measured with HIP
+ * events on its stream while cbx_plan_set_profiling is on (zeros otherwise). */
+int cbx_filter_pass_times(cbx_plan* plan, float* test_ms, float* scan_ms, float* emit_ms);
 
 /* ---- the record walk with data-dependent offsets ----
  *
