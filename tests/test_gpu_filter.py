@@ -5,6 +5,7 @@ value identical, generated ids included.
 """
 from __future__ import annotations
 
+import random
 from decimal import Decimal
 
 import numpy as np
@@ -17,11 +18,16 @@ pytestmark = pytest.mark.gpu
 from cobrix_amd import filter as F  # noqa: E402
 from cobrix_amd import native as N  # noqa: E402
 from cobrix_amd.options import parse_options  # noqa: E402
-from cobrix_amd.reader import FixedLenNestedReader, ReaderParameters, VarLenNestedReader  # noqa: E402
+from cobrix_amd.reader import (FixedLenNestedReader, ReaderParameters, VarLenNestedReader,  # noqa: E402
+                               parse_copybook_for)
 from cobrix_amd.synth import RDW_NARROW_COPYBOOK, SYN200_COPYBOOK, rdw_file, rdw_narrow, syn200  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from oracle import reader_oracle as RO  # noqa: E402
-from test_filter import py_keep, row_value  # noqa: E402
+from parity import compare_batch  # noqa: E402
+from test_decode_fuzz import ASCII_COPYBOOK, FUZZ_COPYBOOK  # noqa: E402
+from test_filter import (FUZZ_N, LADDER_COPYBOOK, NARROW_SEGMENTS, ascii_records, check_field_filters,  # noqa: E402
+                         expected_keep, field_filters, fuzz_records, ladder_file, ladder_params, narrow_file,
+                         narrow_params, py_keep, row_value)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -405,4 +411,370 @@ def test_hierarchical_read_with_filters_raises():
         rd.read(raw, filters=[F.EqualTo("SEGMENT-ID", "C")])
     assert e.value.code == N.CBX_E_UNSUPPORTED
     assert len(rd.read(raw).to_rows()) > 0
+    rd.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# Every decoder kind and edge: test_filter.py's filter families (one per field of a copybook) on the GPU.
+# The bulk of a family is compared as a selection (the kept records' indices against the contract over
+# the oracle's rows); one filter per field goes through the whole filtered read and its rows are compared.
+# ---------------------------------------------------------------------------------------------
+def _flags(ids, n: int, what) -> np.ndarray:
+    """Keep flags of n records from a selection's record indices, which must be in file order."""
+    ids = np.asarray(ids, dtype=np.int64)
+    assert ids.size == 0 or (ids[0] >= 0 and ids[-1] < n and (np.diff(ids) > 0).all()), (what, ids[:10], n)
+    keep = np.zeros(n, dtype=bool)
+    keep[ids] = True
+    return keep
+
+
+def _same(a, b) -> bool:
+    """Row values equal; COMP-1 / COMP-2 values (numpy scalars, NaNs among them for random bytes) as bit patterns."""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return isinstance(b, (list, tuple)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.floating) and isinstance(b, np.floating):   # bit for bit, a NaN's payload included
+        return a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    return a == b
+
+
+def _rows_match(got, exp, what):
+    assert len(got) == len(exp), (what, len(got), len(exp))
+    bad = [i for i, (a, b) in enumerate(zip(got, exp)) if not _same(a, b)]
+    diff = {k: (got[bad[0]].get(k), exp[bad[0]].get(k)) for k in exp[bad[0]] if not _same(got[bad[0]].get(k), exp[bad[0]].get(k))} \
+        if bad else {}
+    assert not bad, (what, bad[:5], diff)
+
+
+def _one_filter_per_field(family, expected):
+    """Of every field's compiled filters one that keeps and drops rows (any, where none does): the one that
+    keeps the fewest rows for every second field, for the others the one nearest a tenth of the rows (the
+    rows of a batch are rebuilt in Python: a few dozen per field keep the test quick)."""
+    by = {}
+    for name, f in family:
+        e = expected.get(id(f))
+        if e is not None:
+            by.setdefault(name, []).append((int(e.sum()), len(by.get(name, ())), f, len(e)))
+    picks = []
+    for k, lst in enumerate(by.values()):
+        sep = [x for x in lst if 0 < x[0] < x[3]] or lst
+        picks.append((min(sep) if k % 2 else min(sep, key=lambda x: (abs(x[0] - x[3] // 10), x[1])))[2])
+    return picks
+
+
+def _run_fixed(rd, t, n_bytes, cb, rows, family, expected, first_record_id=0, **kw):
+    """A family over fixed-length records in HBM: selections through cbx_filter_records, then one filtered
+    decode_device per field."""
+    stride = rd.get_record_size()
+    n = n_bytes // stride
+    assert n == len(rows)
+    st = torch.cuda.current_stream()
+
+    def keep_fn(table, f):
+        sel = rd._filter_records(table, t, n_bytes, n, st, stride=stride, first_record_id=first_record_id)
+        return _flags(sel["record_id"][:sel["n"]].cpu().numpy() - first_record_id, n, f)
+    count = check_field_filters(cb, rd.plan, rows, family, keep_fn, expected=expected, **kw)
+    for f in _one_filter_per_field(family, expected):
+        b = rd.decode_device(t, n_bytes, first_record_id, filters=[f])
+        assert b.unhandled_filters == []
+        _rows_match(b.to_rows(), [r for r, k in zip(rows, expected[id(f)]) if k], f)
+    return count
+
+
+def _run_framed(rd, raw, cb, rows, family, expected, path, **kw):
+    """A family over a variable-length file: `read` (select -> filter -> decode_selected) or `decode` (the framed
+    records straight into the filter stage, the active segment from the plan's segment map)."""
+    t = rd._device_file(raw)
+    off, ln, vb = rd.frame_file(t, len(raw))
+    n = int(off.numel())
+    assert n == len(rows)
+    src = rd.select(t, vb, off, ln, None, 0) if path == "read" else (off, ln)
+    assert path != "read" or src["n"] == n
+    host_off = off.cpu().numpy()
+
+    def keep_fn(table, f):
+        sel = rd.filter(t, vb, src, [f])
+        assert sel["unhandled"] == []
+        k = sel["n"]
+        ids = np.searchsorted(host_off, sel["rec_off"][:k].cpu().numpy())
+        assert np.array_equal(host_off[ids], sel["rec_off"][:k].cpu().numpy())
+        assert np.array_equal(sel["rec_len"][:k].cpu().numpy(), ln.cpu().numpy()[ids])
+        assert np.array_equal(sel["record_id"][:k].cpu().numpy(), ids), f     # Record_Id = index in the file
+        return _flags(ids, n, f)
+    count = check_field_filters(cb, rd.plan, rows, family, keep_fn, expected=expected, **kw)
+    for f in _one_filter_per_field(family, expected):
+        b = rd.read(raw, filters=[f]) if path == "read" else rd.decode(raw, filters=[f])
+        assert b.unhandled_filters == []
+        _rows_match(b.to_rows(), [r for r, k in zip(rows, expected[id(f)]) if k], f)
+    return count
+
+
+_CASES: dict = {}   # inputs, oracle rows, families and their expected flags: computed once, shared, never changed
+
+
+def _case(key, make):
+    if key not in _CASES:
+        _CASES[key] = make()
+    return _CASES[key]
+
+
+def _device(data: bytes, odd: bool = False):
+    t = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+    if not odd:
+        return t.cuda()
+    buf = torch.zeros(len(data) + 9, dtype=torch.uint8, device="cuda")   # a batch cut out of a larger buffer
+    buf[9:] = t.cuda()
+    return buf[9:]
+
+
+# the option sets of test_gpu_parity.test_fuzz_copybook_vs_oracle
+FUZZ_GPU_OPTIONS = [("common", "both", "IBM"), ("cp037", "left", "IEEE754"), ("cp875", "none", "IBM_LE")]
+FUZZ_UNHANDLED = dict(unhandled_names=("F01", "F02"), reason="COMP-1 / COMP-2")
+
+
+def _fuzz_case(code_page, trim, fmt, start, end):
+    def make():
+        p = ReaderParameters(schema_policy="collapse_root", ebcdic_code_page=code_page, string_trimming_policy=trim,
+                             floating_point_format=fmt, start_offset=start, end_offset=end)
+        cb = parse_copybook_for(FUZZ_COPYBOOK, p)
+        data = fuzz_records(cb, FUZZ_N, 31, start, end)
+        rows = RO.fixed_len_rows(cb, data, p)
+        assert len(rows) == FUZZ_N
+        return p, cb, data, rows, list(field_filters(cb, rows, random.Random(17))), {}
+    return _case(("fuzz", code_page, trim, fmt, start, end), make)
+
+
+@pytest.mark.parametrize("mode", ["plain", "offsets", "odd_pointer"])
+@pytest.mark.parametrize("code_page,trim,fmt", FUZZ_GPU_OPTIONS)
+def test_fuzz_copybook_field_filters(code_page, trim, fmt, mode):
+    """Every zoned / binary / COMP-3 shape of the decode fuzz, three strings and null tests on two floats, 321
+    records (two workgroups, the second with one record): plain, with record_start_offset 3 and
+    record_end_offset 2 (random bytes there), and at an odd device address."""
+    start, end = (3, 2) if mode == "offsets" else (0, 0)
+    p, cb, data, rows, family, expected = _fuzz_case(code_page, trim, fmt, start, end)
+    rd = FixedLenNestedReader(FUZZ_COPYBOOK, p)
+    n = _run_fixed(rd, _device(data, odd=mode == "odd_pointer"), len(data), cb, rows, family, expected, **FUZZ_UNHANDLED)
+    assert n > 1000
+    rd.close()
+
+
+@pytest.mark.parametrize("code_page,trim,fmt", FUZZ_GPU_OPTIONS)
+def test_fuzz_copybook_single_record(code_page, trim, fmt):
+    """One record at the start of the data: a field that ends before byte 16 has no 16 bytes in front of its
+    end, so the SWAR forms hand it to the byte loop.  The literals are those of the 321-record family."""
+    p, cb, data, rows, family, _ = _fuzz_case(code_page, trim, fmt, 0, 0)
+    rd = FixedLenNestedReader(FUZZ_COPYBOOK, p)
+    one = data[:cb.record_size]
+    n = _run_fixed(rd, _device(one), len(one), cb, rows[:1], family, {}, separation=0, **FUZZ_UNHANDLED)
+    assert n > 1000
+    rd.close()
+
+
+@pytest.mark.parametrize("charset", ["", "windows-1252"])
+def test_ascii_copybook_field_filters(charset):
+    """ASCII data: every CBX_K_ASCII_NUM shape, the ASCII string through ascii_lut or the charset's table."""
+    def make():
+        p = ReaderParameters(schema_policy="collapse_root", is_ebcdic=False, ascii_charset=charset)
+        cb = parse_copybook_for(ASCII_COPYBOOK, p)
+        data = ascii_records(cb, FUZZ_N, 32)
+        rows = RO.fixed_len_rows(cb, data, p)
+        return p, cb, data, rows, list(field_filters(cb, rows, random.Random(18))), {}
+    p, cb, data, rows, family, expected = _case(("ascii", charset), make)
+    rd = FixedLenNestedReader(ASCII_COPYBOOK, p)
+    n = _run_fixed(rd, _device(data), len(data), cb, rows, family, expected, unhandled_names=("N1", "N2", "N3"),
+                   reason="UTF-16", null_tests_compile=False)
+    assert n > 300
+    rd.close()
+
+
+@pytest.mark.parametrize("path", ["read", "decode"])
+@pytest.mark.parametrize("trim", ["none", "left", "right", "both"])
+def test_width_ladder_on_cut_records(trim, path):
+    """Strings of 1-47 bytes (in registers up to 32 bytes, through the pointer beyond), COMP-3 and zoned of 1-16
+    bytes on 500 RDW records cut at random lengths, under the four trimming policies."""
+    def make():
+        p = ladder_params(trim)
+        cb = parse_copybook_for(LADDER_COPYBOOK, p)
+        raw, _, _ = ladder_file()
+        rows = RO.var_len_rows(cb, raw, p)
+        return p, cb, raw, rows, list(field_filters(cb, rows, random.Random(19))), {}
+    p, cb, raw, rows, family, expected = _case(("ladder", trim), make)
+    rd = VarLenNestedReader(LADDER_COPYBOOK, p)
+    n = _run_framed(rd, raw, cb, rows, family, expected, path)
+    assert n > 950
+    rd.close()
+
+
+@pytest.mark.parametrize("trim", ["none", "both"])
+def test_width_ladder_cut_at_every_length(trim):
+    """One ladder record per length 1..L (framed source): every field cut after each of its bytes."""
+    def make():
+        p = ladder_params(trim)
+        cb = parse_copybook_for(LADDER_COPYBOOK, p)
+        raw, _, ln = ladder_file(seed=34, every_length=True)
+        assert ln.tolist() == list(range(1, cb.record_size + 1))
+        rows = RO.var_len_rows(cb, raw, p)
+        return p, cb, raw, rows, list(field_filters(cb, rows, random.Random(26))), {}
+    p, cb, raw, rows, family, expected = _case(("ladder_every", trim), make)
+    rd = VarLenNestedReader(LADDER_COPYBOOK, p)
+    assert _run_framed(rd, raw, cb, rows, family, expected, "decode") > 950
+    rd.close()
+
+
+@pytest.mark.parametrize("start,delta", [(0, 17 - 517), (0, -150), (5, 98)])
+def test_record_length_shorter_and_longer_than_the_copybook(start, delta):
+    """record_length (the pattern of test_gpu_parity.test_record_offsets_and_length) on FUZZ_COPYBOOK: 17 bytes
+    (S1 and S2 whole, A1 cut after two bytes, every numeric past the record: null), 150 bytes short (the
+    COMP-3 fields and the floats past the record), 98 bytes long behind a start offset of 5."""
+    p0 = ReaderParameters(schema_policy="collapse_root", ebcdic_code_page="cp037")
+    size = parse_copybook_for(FUZZ_COPYBOOK, p0).record_size
+    assert size == 517
+    rl = size + delta
+    n_rec = 130
+
+    def make():
+        p = ReaderParameters(schema_policy="collapse_root", ebcdic_code_page="cp037", start_offset=start, record_length=rl)
+        cb = parse_copybook_for(FUZZ_COPYBOOK, p)
+        base = fuzz_records(cb, n_rec, 41)
+        rng = np.random.default_rng(1)
+        data = bytearray()
+        for i in range(n_rec):
+            r = base[i * size:(i + 1) * size] + bytes(rng.integers(0, 256, max(0, rl - size), dtype=np.uint8))
+            data += bytes(rng.integers(0, 256, start, dtype=np.uint8)) + r[:rl]
+        rows = RO.fixed_len_rows(cb, bytes(data), p)
+        assert len(rows) == n_rec
+        return p, cb, bytes(data), rows, list(field_filters(cb, rows, random.Random(23))), {}
+    p, cb, data, rows, family, expected = _case(("record_length", start, delta), make)
+    if delta < 0:
+        assert all(r["P17"] is None and r["F02"] is None for r in rows) and any(r["S1"] for r in rows)
+    if rl == 17:
+        assert all(r["Z01"] is None and len(r["A1"]) <= 2 for r in rows) and any(len(r["A1"]) == 2 for r in rows)
+    rd = FixedLenNestedReader(FUZZ_COPYBOOK, p)
+    assert rd.get_record_size() == rl + start
+    # fields past a short record are null in every row: their null tests cannot keep and drop rows
+    n = _run_fixed(rd, _device(data), len(data), cb, rows, family, expected,
+                   **({"separation": 0} if delta < 0 else {}), **FUZZ_UNHANDLED)
+    assert n > (1000 if delta > 0 else 50)
+    rd.close()
+
+
+def test_segment_map_without_levels_fixed():
+    """Fixed-length records of the test5 layout (test_gpu_parity.test_segment_redefines_fixed) with the
+    redefine map and no Seg_Id levels: the filter stage takes each record's active segment from the plan's
+    segment map and hands it to the decode.  Some records carry an id the map does not name."""
+    p = ReaderParameters(schema_policy="collapse_root", segment_field="SEGMENT-ID",
+                         segment_id_redefine_map=dict(NARROW_SEGMENTS))
+    cb = parse_copybook_for(RDW_NARROW_COPYBOOK, p)
+    raw = narrow_file(FUZZ_N, 22)
+    off, ln = O.frame_rdw(raw)
+    L = cb.record_size
+    data = b"".join((raw[o:o + l] + b"\x40" * L)[:L] for o, l in zip(off, ln))
+    rows = RO.fixed_len_rows(cb, data, p)
+    assert len(rows) == FUZZ_N
+    assert all(any(r[g] is not None for r in rows) for g in ("STATIC_DETAILS", "CONTACTS"))
+    assert any(r["STATIC_DETAILS"] is None and r["CONTACTS"] is None for r in rows)
+    rd = FixedLenNestedReader(RDW_NARROW_COPYBOOK, p)
+    assert rd.plan.options.has_segments and not rd.plan.seg_id_columns
+    family = list(field_filters(cb, rows, random.Random(24)))
+    assert _run_fixed(rd, _device(data), len(data), cb, rows, family, {}) > 150
+    rd.close()
+
+
+def test_segment_map_without_levels_framed():
+    """RDW_NARROW through decode(raw, filters=...): framed records, segment_field and the redefine map but no
+    segment_id_level*, so no select() stage gives the segments."""
+    p = narrow_params()
+    cb = parse_copybook_for(RDW_NARROW_COPYBOOK, p)
+    raw = narrow_file(FUZZ_N, 21)
+    rows = RO.var_len_rows(cb, raw, p)
+    assert all(any(r[g] is not None for r in rows) for g in ("STATIC_DETAILS", "CONTACTS"))
+    assert any(r["STATIC_DETAILS"] is None and r["CONTACTS"] is None for r in rows)
+    rd = VarLenNestedReader(RDW_NARROW_COPYBOOK, p)
+    assert rd.plan.options.has_segments and not rd.plan.seg_id_columns
+    family = list(field_filters(cb, rows, random.Random(25)))
+    assert _run_framed(rd, raw, cb, rows, family, {}, "decode") > 150
+    rd.close()
+
+
+def test_first_record_id_carried_into_a_fixed_selection(syn):
+    rd, recs, rows = syn
+    n = 130
+    data = recs[:n].numpy().tobytes()
+    t = _device(data)
+    for key, filters in syn_predicates(rd.copybook, rows).items():
+        exp = np.nonzero(expected_keep(rd.copybook, rows[:n], filters))[0]
+        table, un = F.compile_filters(rd.plan, filters)
+        assert not un
+        sel = rd._filter_records(table, t, len(data), n, torch.cuda.current_stream(), stride=200, first_record_id=1000)
+        assert sel["n"] == len(exp), key
+        assert np.array_equal(sel["record_id"][:sel["n"]].cpu().numpy(), 1000 + exp), key
+        assert np.array_equal(sel["rec_off"][:sel["n"]].cpu().numpy(), 200 * exp), key
+        b = rd.decode_device(t, len(data), 1000, filters=filters)
+        _check(b.to_rows(), rows[:n], rd.copybook, filters, b.unhandled_filters)
+
+
+# ---------------------------------------------------------------------------------------------
+# Filtered reads in the three string layouts, on the table-driven and the specialised kernel
+# ---------------------------------------------------------------------------------------------
+def _share_filters(cb, rows, name):
+    """Five filters on `name` that keep none, one, about a tenth, about half and all of the rows; the literals
+    are the oracle's values."""
+    vals = sorted(v for v in (row_value(cb, r, name) for r in rows) if v is not None)
+    once = next(v for v in vals if vals.count(v) == 1)
+    return {"none": F.LessThan(name, vals[0]), "one": F.EqualTo(name, once),
+            "tenth": F.LessThan(name, vals[len(vals) // 10]), "half": F.LessThan(name, vals[len(vals) // 2]),
+            "all": F.Or(F.IsNull(name), F.GreaterThanOrEqual(name, vals[0]))}
+
+
+def _layout_case(which):
+    def make():
+        if which == "syn200":
+            text, kw, name = SYN200_COPYBOOK, {}, "ACCT-NO"
+            cb = parse_copybook_for(text, ReaderParameters(schema_policy="collapse_root"))
+            data = syn200(SYN_N, seed=11, malformed_rate=0.2).numpy().tobytes()
+        else:
+            text, kw, name = FUZZ_COPYBOOK, dict(ebcdic_code_page="cp037", string_trimming_policy="left"), "B07"
+            cb = parse_copybook_for(text, ReaderParameters(schema_policy="collapse_root", **kw))
+            data = fuzz_records(cb, FUZZ_N, 31)
+        rows = RO.fixed_len_rows(cb, data, ReaderParameters(schema_policy="collapse_root", **kw))
+        filters = _share_filters(cb, rows, name)
+        kept = {k: np.nonzero(expected_keep(cb, rows, [f]))[0] for k, f in filters.items()}
+        n = len(rows)
+        assert len(kept["none"]) == 0 and len(kept["one"]) == 1 and len(kept["all"]) == n
+        assert n // 20 < len(kept["tenth"]) < n // 5 and n // 3 < len(kept["half"]) < 2 * n // 3
+        return text, kw, cb, data, filters, kept
+    return _case(("layout", which), make)
+
+
+@pytest.mark.parametrize("jit", [1, -1])
+@pytest.mark.parametrize("layout", ["large", "views", "utf8"])
+@pytest.mark.parametrize("which", ["syn200", "fuzz"])
+def test_filtered_read_layouts_and_kernels(which, layout, jit):
+    """A filtered fixed-length read decodes the kept records through the offset / length path: in the large,
+    string-view and Utf8 layouts, with the specialised kernel allowed from one record on and switched off,
+    every column equals the oracle's decode of exactly the kept records' bytes."""
+    text, kw, cb, data, filters, kept = _layout_case(which)
+    rd = FixedLenNestedReader(text, ReaderParameters(schema_policy="collapse_root", jit_min_records=jit,
+                                                     string_views=layout == "views", string_utf8=layout == "utf8", **kw))
+    size = rd.get_record_size()
+    t = _device(data)
+    for key, f in filters.items():
+        idx = kept[key]
+        b = rd.decode_device(t, len(data), filters=[f])
+        assert b.unhandled_filters == [] and b.n_rec == len(idx), (key, b.n_rec, len(idx))
+        if len(idx) == 0:
+            continue
+        sub = b"".join(data[i * size:(i + 1) * size] for i in idx)
+        errs = compare_batch(b, O.decode_fixed(rd.copybook, sub))
+        assert not errs, (key, errs)
+        if layout == "utf8":
+            pitch = 64 * ((b.n_rec + 63) // 64)
+            for ci, info in enumerate(rd.plan.columns):
+                c = b.cols[ci]
+                if "offsets32" not in c:
+                    continue
+                o = c["offsets32"].cpu().numpy().reshape(info.n_slots, pitch + 1)[:, :b.n_rec + 1].astype(np.int64)
+                assert (o[:, 0] == 0).all() and (np.diff(o, axis=1) >= 0).all(), (key, ci)
+                assert np.array_equal(o[:, -1], c["sizes"].cpu().numpy()), (key, ci)
     rd.close()
