@@ -27,6 +27,7 @@
 #include "cbx_walk.h"
 #include "cbx_chain.h"
 #include "cbx_filter.h"
+#include "cbx_gather.h"
 
 using namespace cbx;
 
@@ -166,6 +167,13 @@ struct cbx_plan {
     struct CallEvents { hipEvent_t e[3]; };
     std::vector<CallEvents> ev_calls;    // recorded, not yet read
     float flt_ms[3] = {0.f, 0.f, 0.f};   // test / scan / emit of the last cbx_filter_records call (profiling)
+    // the direct projected decode (cbx_gather.h; cbx_plan_options.direct_decode)
+    bool direct_ok = false;              // the plan's shape is one the direct kernel decodes
+    std::string direct_why;              // why not
+    std::vector<GatherOp> gather_ops;
+    GatherOp* d_gather = nullptr;
+    int64_t* d_view_geo = nullptr;       // per call: [n_columns][2] view tile bytes, tiles per data buffer
+    std::vector<int64_t> h_view_geo;
 };
 
 #include "cbx_jit.h"
@@ -559,8 +567,15 @@ extern "C" int cbx_plan_create(const cbx_field* fields, int32_t n_fields, const 
         }
     }
 
+    // ---- the direct projected decode: which plans it takes (cbx_gather.h)
+    if (!P->harrays.empty()) P->direct_why = "the plan has OCCURS arrays";
+    else if (!P->segid_cols.empty()) P->direct_why = "the plan has Seg_Id level columns";
+    else if (P->n_seq > 0 && !P->view) P->direct_why = "string columns are not in the string-view layout";
+    else P->direct_ok = gather_build(fields, n_fields, P->gather_ops, P->direct_why);
+
     int r;
-    if ((r = upload(&P->d_fields, P->dfields_h.data(), P->dfields_h.size())) ||
+    if ((r = upload(&P->d_gather, P->gather_ops.data(), P->direct_ok ? P->gather_ops.size() : 0)) ||
+        (r = upload(&P->d_fields, P->dfields_h.data(), P->dfields_h.size())) ||
         (r = upload_set(P->cset)) || (r = upload_set(P->wset)) ||
         (r = upload(&P->d_arrays, P->harrays.data(), P->harrays.size())) ||
         (r = upload(&P->d_defer, P->hdefer.data(), P->hdefer.size())) ||
@@ -571,6 +586,7 @@ extern "C" int cbx_plan_create(const cbx_field* fields, int32_t n_fields, const 
     }
     if (opts->has_segments && (r = upload(&P->d_segmap, &sm, 1))) { cbx_plan_destroy(P); return r; }
     if (hipMalloc((void**)&P->d_cols, sizeof(DevColumn) * P->n_columns) != hipSuccess ||
+        hipMalloc((void**)&P->d_view_geo, sizeof(int64_t) * 2 * P->n_columns) != hipSuccess ||
         hipMalloc((void**)&P->d_seqcall, sizeof(SeqCall) * std::max(1, P->n_seq)) != hipSuccess ||
         hipMalloc((void**)&P->d_status, 64) != hipSuccess ||
         hipMemset(P->d_status, 0, 64) != hipSuccess) {
@@ -597,6 +613,7 @@ extern "C" void cbx_plan_destroy(cbx_plan* P) {
     (void)hipFree(P->d_wnodes); (void)hipFree(P->d_warr); (void)hipFree(P->d_whand); (void)hipFree(P->d_wslot_base);
     (void)hipFree(P->d_wtile_bytes); (void)hipFree(P->d_wcursor);
     (void)hipFree(P->d_wvbase); (void)hipFree(P->d_wvcol); (void)hipFree(P->d_wvslot);
+    (void)hipFree(P->d_gather); (void)hipFree(P->d_view_geo);
     for (auto& e : P->ev_pool) (void)hipEventDestroy(e);
     for (auto& c : P->ev_calls) for (auto& e : c.e) if (e) (void)hipEventDestroy(e);
     if (P->pipe_peer) P->pipe_peer->pipe_peer = nullptr;
@@ -1408,6 +1425,70 @@ static int walk_launch(cbx_plan* P, const CallShape& c, cbx_column* columns, hip
     return CBX_OK;
 }
 
+// Why the plan's decode calls do not run the direct kernel (cbx_gather.h); empty: they do.
+static std::string direct_refusal(const cbx_plan* P) {
+    if (P->walk) return "the plan decodes through the record walk";
+    if (!P->direct_ok) return P->direct_why;
+    if (P->pipe_peer) return "the plan is pipelined with a peer (cbx_plan_pipeline)";
+    return "";
+}
+
+// The direct projected decode of one call: column table + view geometry uploaded stream-ordered, one kernel.
+static int gather_launch(cbx_plan* P, const CallShape& c, const cbx_column* columns, hipStream_t st) {
+    const int64_t n_tiles = (c.n_rec + kWave - 1) / kWave;
+    P->last_kind = 4;
+    if (n_tiles == 0) return CBX_OK;
+    P->h_cols.resize(P->n_columns);
+    P->h_view_geo.assign(2 * (size_t)P->n_columns, 0);
+    for (int i = 0; i < P->n_columns; i++) {
+        DevColumn d{};
+        d.values = columns[i].values;
+        d.validity = columns[i].validity;
+        d.offsets = columns[i].offsets;
+        d.data = columns[i].data;
+        d.capacity = columns[i].data_capacity;
+        d.sizes = columns[i].data_sizes;
+        P->h_cols[i] = d;
+        if (P->col_is_string[i]) {
+            P->h_view_geo[2 * i] = view_tile_bytes(P, i);
+            P->h_view_geo[2 * i + 1] = view_tiles_per_buf(P->h_view_geo[2 * i]);
+        }
+    }
+    auto written = [&](int i) { return columns[i].values && columns[i].validity; };
+    for (const GatherOp& g : P->gather_ops)
+        if (!written(g.f.column)) return fail(CBX_E_ARGUMENT, "column " + std::to_string(g.f.column) + ": values and validity buffers required");
+    if (P->seg_col >= 0 && !written(P->seg_col)) return fail(CBX_E_ARGUMENT, "segment column: values and validity buffers required");
+    HIP_CHECK(hipMemcpyAsync(P->d_cols, P->h_cols.data(), sizeof(DevColumn) * P->n_columns, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(P->d_view_geo, P->h_view_geo.data(), sizeof(int64_t) * P->h_view_geo.size(), hipMemcpyHostToDevice, st));
+    GatherArgs a{};
+    a.data = c.data; a.n_bytes = c.data_len;
+    a.rec_off = c.rec_off; a.rec_len = c.rec_len; a.rec_seg = c.rec_seg; a.rec_id = c.rec_id;
+    a.rec_id_base = P->d_rec_base;
+    a.n = c.n_rec; a.n_tiles = n_tiles; a.first_record_id = c.first_record_id;
+    a.stride = c.stride; a.start_off = c.start_off;
+    a.file_id = c.file_id >= 0 ? c.file_id : P->opts.file_id;
+    a.n_ops = (int32_t)P->gather_ops.size();
+    a.seg_col = P->seg_col;
+    a.ops = (const CBX_CONST GatherOp*)P->d_gather;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.cols = (const CBX_CONST DevColumn*)P->d_cols;
+    a.view_geo = (const CBX_CONST int64_t*)P->d_view_geo;
+    a.lut = P->d_lut;
+    cbx_plan::CallEvents ce{{nullptr, nullptr, nullptr}};   // e[2] stays null: no post passes (post_ms 0)
+    if (P->profiling) {
+        for (int k = 0; k < 2; k++) if (!(ce.e[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ce.e[0], st));
+    }
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((n_tiles + kGthThreads / kWave - 1) / (kGthThreads / kWave))), dim3(kGthThreads), 0, st, a);
+    HIP_CHECK(hipGetLastError());
+    if (P->profiling) {
+        HIP_CHECK(hipEventRecord(ce.e[1], st));
+        P->ev_calls.push_back(ce);
+    }
+    return CBX_OK;
+}
+
 static int decode_common(cbx_plan* P, const CallShape& c, cbx_column* columns, int64_t* sizes_only, hipStream_t st) {
     if (!P || !c.data || c.n_rec < 0 || c.start_off < 0) return fail(CBX_E_ARGUMENT, "invalid decode arguments");
     if (!sizes_only && !columns) return fail(CBX_E_ARGUMENT, "columns required");
@@ -1448,7 +1529,16 @@ static int decode_common(cbx_plan* P, const CallShape& c, cbx_column* columns, i
             return fail(CBX_E_ARGUMENT, "column " + std::to_string(i) + ": string buffers required");
         }
     }
+    if (P->opts.direct_decode == 1 && direct_refusal(P).empty()) return gather_launch(P, c, columns, st);
     return launch(P, c, columns, 0, st);
+}
+
+extern "C" int cbx_plan_direct_eligible(const cbx_plan* P, int32_t* eligible) {
+    if (!P || !eligible) return fail(CBX_E_ARGUMENT, "cbx_plan_direct_eligible: invalid arguments");
+    const std::string why = direct_refusal(P);
+    *eligible = why.empty() ? 1 : 0;
+    if (!why.empty()) g_err = "direct decode: " + why;
+    return CBX_OK;
 }
 
 extern "C" int cbx_plan_check(cbx_plan* P, void* stream) {
@@ -1566,16 +1656,16 @@ extern "C" int cbx_plan_kernel_times(cbx_plan* P, float* decode_ms, float* fixup
     if (!P || !n_calls || max_calls < 0) return fail(CBX_E_ARGUMENT, "cbx_plan_kernel_times: invalid arguments");
     int n = 0;
     for (auto& c : P->ev_calls) {
-        HIP_CHECK(hipEventSynchronize(c.e[2]));
+        HIP_CHECK(hipEventSynchronize(c.e[2] ? c.e[2] : c.e[1]));   // (e[2] null: a call without post passes)
         if (n < max_calls) {
             float d = 0, f = 0;
             HIP_CHECK(hipEventElapsedTime(&d, c.e[0], c.e[1]));
-            HIP_CHECK(hipEventElapsedTime(&f, c.e[1], c.e[2]));
+            if (c.e[2]) HIP_CHECK(hipEventElapsedTime(&f, c.e[1], c.e[2]));
             if (decode_ms) decode_ms[n] = d;
             if (fixup_ms) fixup_ms[n] = f;
             n++;
         }
-        for (auto& e : c.e) P->ev_pool.push_back(e);
+        for (auto& e : c.e) if (e) P->ev_pool.push_back(e);
     }
     P->ev_calls.clear();
     *n_calls = n;

@@ -44,8 +44,8 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_hier_list_offsets", "cbx_plan_set_walk", "cbx_frame_var_occurs",
                     "cbx_plan_set_record_base", "cbx_frame_length_field", "cbx_plan_set_odo_counts",
                     "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline",
-                    "cbx_filter_records", "cbx_filter_pass_times")
-ABI_VERSION = 21
+                    "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible")
+ABI_VERSION = 22
 
 
 class NativeLibraryError(RuntimeError):
@@ -93,7 +93,7 @@ class CbxSegmentMap(ctypes.Structure):
 class CbxPlanOptions(ctypes.Structure):
     _fields_ = [("n_columns", ctypes.c_int32), ("file_id", ctypes.c_int32), ("has_segments", ctypes.c_int32),
                 ("window_bytes", ctypes.c_int32), ("segment_column", ctypes.c_int32),
-                ("jit_min_records", ctypes.c_int32), ("string_views", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("jit_min_records", ctypes.c_int32), ("string_views", ctypes.c_int32), ("direct_decode", ctypes.c_int32),
                 ("lut", ctypes.c_uint32 * 256),
                 ("segments", CbxSegmentMap)]
 
@@ -258,7 +258,8 @@ def load():
                      ("cbx_views_to_utf8", [P, i64, P, i64, P, P, i64, P, P]),
                      ("cbx_plan_pipeline", [P, P, i32, i32]),
                      ("cbx_filter_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, P]),
-                     ("cbx_filter_pass_times", [P, P, P, P])):
+                     ("cbx_filter_pass_times", [P, P, P, P]),
+                     ("cbx_plan_direct_eligible", [P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):

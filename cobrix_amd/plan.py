@@ -59,6 +59,18 @@ class DecodePlan:
     file_id_column: int = -1
     seg_id_columns: List[int] = field(default_factory=list)   # Seg_Id0.. string columns
     walk: Optional["WalkTables"] = None                          # record-walk tables (cbx_plan_set_walk)
+    # column projection (build_plan(columns=...)): id(Primitive) of the requested fields; None: all
+    projected: Optional[frozenset] = None
+
+    def keeps(self, st: cbk.Statement) -> bool:
+        """Whether `st` appears in a row / Arrow struct / schema of this plan: a requested primitive,
+        or a group (an OCCURS) with one below it.  Without a projection: everything."""
+        if self.projected is None:
+            return True
+        cache = self.__dict__.setdefault("_keeps", {})
+        if id(st) not in cache:
+            cache[id(st)] = keeps_node(st, self.projected)
+        return cache[id(st)]
 
     @property
     def n_columns(self) -> int:
@@ -149,19 +161,68 @@ def segment_keys(redefine_map: Dict[str, str], levels: List[str], seg_filter: Op
     return keys
 
 
+def project_columns(cb: cbk.Copybook, columns: Sequence[str]) -> frozenset:
+    """The primitives a projection keeps, as id(Primitive): every requested name resolved as a filter
+    attribute is (Copybook.get_field_by_name: dotted paths, group names; its ValueError for an unknown
+    or ambiguous one) -- a primitive itself, a group every primitive below it."""
+    if isinstance(columns, str):
+        raise TypeError("columns must be a sequence of field names, not a string")
+    kept = set()
+    for name in columns:
+        st = cb.get_field_by_name(name)
+        kept.update(id(q) for q in (_iter_prims(st) if isinstance(st, cbk.Group) else [st]))
+    return frozenset(kept)
+
+
+def keeps_node(st: cbk.Statement, kept: frozenset) -> bool:
+    if isinstance(st, cbk.Group):
+        return any(keeps_node(c, kept) for c in st.children)
+    return id(st) in kept
+
+
 def build_plan(cb: cbk.Copybook, *, segment_field: Optional[str] = None,
                segment_redefine_map: Optional[Dict[str, str]] = None, generate_record_id: bool = False,
                file_id: int = 0, window_bytes: int = 0, jit_min_records: int = 0,
                segment_levels: Sequence[str] = (), segment_filter: Optional[List[str]] = None,
                segment_prefix: str = "", string_views: int = 0, occurs_lists: bool = False,
-               root_keys: Sequence[str] = (), walk: bool = False, variable_size_occurs: bool = False) -> DecodePlan:
+               root_keys: Sequence[str] = (), walk: bool = False, variable_size_occurs: bool = False,
+               columns: Optional[Sequence[str]] = None, direct_decode: int = 0) -> DecodePlan:
     """root_keys: segment ids of a hierarchical file's root segment (sparse-index cuts at level-0
     keys, IndexGenerator.scala:89-113, without Seg_IdN columns).  walk: the plan decodes through the
     record walk (cbx_walk.h) -- count columns of nested OCCURS get one slot per enclosing element,
-    dependees inside OCCURS and string dependees (occurs_mappings) are allowed, no list layout."""
+    dependees inside OCCURS and string dependees (occurs_mappings) are allowed, no list layout.
+    columns: column projection (PrunedFilteredScan's requiredColumns) -- the plan holds the requested
+    fields (project_columns), the OCCURS arrays enclosing one with their count columns and, as hidden
+    columns, what those need: the arrays' DEPENDING ON sources and an integral segment-id field.  A
+    record-walk plan keeps every array and every DEPENDING ON source (each moves the offsets behind it;
+    hidden unless requested); its other unrequested primitives become field = -1 walk nodes.  The segment
+    map, segment_groups, the Seg_Id levels and the code-page table are the full plan's; None: the full
+    plan.  direct_decode: cbx_plan_options.direct_decode."""
+    kept = project_columns(cb, columns) if columns is not None else None
+    need: set = set()            # id(Primitive): decoded for a dependency (hidden unless requested)
+    kept_arrays: set = set()     # id(Statement) of the OCCURS nodes the projected plan holds
+    if kept is not None:
+        all_prims = list(_iter_prims(cb.ast))
+
+        def mark(st: cbk.Statement) -> bool:
+            has = any([mark(c) for c in st.children]) if isinstance(st, cbk.Group) else id(st) in kept
+            if st.is_array and (has or walk):
+                kept_arrays.add(id(st))
+                if st.depending_on is not None:
+                    cand = [q for q in all_prims if q.is_dependee and q.name == st.depending_on]
+                    need.update(id(q) for q in cand[:1])
+            return has
+        for rec in cb.ast.children:
+            mark(rec)
+        if walk:   # every dependee registers its value as the walk passes it
+            need.update(id(q) for q in all_prims if q.is_dependee)
+        if segment_field is not None and (segment_redefine_map or segment_levels or segment_filter is not None):
+            sf0 = cb.get_field_by_name(segment_field)
+            if isinstance(sf0, cbk.Primitive) and isinstance(sf0.dtype, cbk.Integral):
+                need.add(id(sf0))
     fields: List[N.CbxField] = []
     arrays: List[N.CbxArray] = []
-    columns: List[ColumnInfo] = []
+    columns: List[ColumnInfo] = []   # (from here on the output columns; the request lives on in `kept`)
     field_of_node: Dict[int, int] = {}
     array_of_node: Dict[int, int] = {}
     seg_groups: List[cbk.Group] = cb.all_segment_redefines()
@@ -176,13 +237,15 @@ def build_plan(cb: cbk.Copybook, *, segment_field: Optional[str] = None,
         columns.append(ci)
         return ci.index
 
-    def visit(st: cbk.Statement, dims: List[Tuple[int, int, int]], segment: int, in_array: bool):
+    def visit(st: cbk.Statement, dims: List[Tuple[int, int, int]], segment: int, in_array: bool, dropped: bool = False):
         counter[0] += 1
         walk_order[id(st)] = counter[0]
         if isinstance(st, cbk.Group) and st.is_segment_redefine:
             segment = seg_index[id(st)]
         my_dims = list(dims)
-        if st.is_array:
+        if st.is_array and kept is not None and id(st) not in kept_arrays:
+            dropped = True   # no requested field below it: neither the array nor its subtree is in the plan
+        if st.is_array and not dropped:
             ai = len(arrays)
             ar = N.CbxArray()
             ar.max_count = st.array_max_size
@@ -196,7 +259,8 @@ def build_plan(cb: cbk.Copybook, *, segment_field: Optional[str] = None,
             outer = 1
             for (cnt, _, _) in dims:
                 outer *= cnt
-            ar.count_column = add_column(kind="count", out_type=N.O_I32, node=st, n_slots=outer if walk else 1)
+            ar.count_column = add_column(kind="count", out_type=N.O_I32, node=st, n_slots=outer if walk else 1,
+                                         hidden=kept is not None and not keeps_node(st, kept))
             ar.offsets_column = -1
             pending_arrays.append((ai, st))
             my_dims.append((st.array_max_size, st.data_size, ai))
@@ -204,10 +268,14 @@ def build_plan(cb: cbk.Copybook, *, segment_field: Optional[str] = None,
                 raise UnsupportedLayout(f"{st.name}: more than {N.CBX_MAX_DIMS} nested OCCURS levels")
         if isinstance(st, cbk.Group):
             for c in st.children:
-                visit(c, my_dims, segment, in_array or st.is_array)
+                visit(c, my_dims, segment, in_array or st.is_array, dropped)
             return
         p: cbk.Primitive = st  # type: ignore[assignment]
+        if p.is_dependee:
+            p.__dict__["_cbx_in_array"] = in_array or p.is_array
         if p.is_filler and not p.is_dependee:
+            return
+        if kept is not None and (dropped or (id(p) not in kept and id(p) not in need)):
             return
         kind, flags = _kind_and_flags(p, cb)
         stp = spark_type(p)
@@ -227,12 +295,9 @@ def build_plan(cb: cbk.Copybook, *, segment_field: Optional[str] = None,
             n_slots *= cnt
         f.segment = segment
         f.column = add_column(kind="value", out_type=f.out_type, n_slots=n_slots, node=p, stype=stp,
-                              hidden=p.is_filler)
+                              hidden=p.is_filler or (kept is not None and id(p) not in kept))
         field_of_node[id(p)] = len(fields)
         fields.append(f)
-        p_in_array = in_array or p.is_array
-        if p.is_dependee:
-            p.__dict__["_cbx_in_array"] = p_in_array
 
     for rec in cb.ast.children:
         visit(rec, [], -1, False)
@@ -348,6 +413,7 @@ def build_plan(cb: cbk.Copybook, *, segment_field: Optional[str] = None,
     opts.window_bytes = window_bytes
     opts.segment_column = seg_col
     opts.jit_min_records = jit_min_records
+    opts.direct_decode = int(direct_decode)
     # 0 Arrow large-string, 1 string views, 2 Arrow Utf8 (int32 offsets, count pass + one decode pass)
     opts.string_views = int(string_views) if string_views in (0, 1, 2) else 1
     # the byte table: the code page (EBCDIC), the charset (ASCII wrapper), or for a US-ASCII copybook
@@ -363,7 +429,7 @@ def build_plan(cb: cbk.Copybook, *, segment_field: Optional[str] = None,
     for i in range(256):
         opts.lut[i] = int(lut[i])
     plan = DecodePlan(cb, fields, arrays, columns, opts, field_of_node, array_of_node, seg_groups,
-                      seg_col, rid_col, fid_col, seg_id_cols)
+                      seg_col, rid_col, fid_col, seg_id_cols, projected=kept)
     if walk:
         plan.walk = walk_tables(plan, variable_size_occurs, has_segments=bool(red))
     return plan

@@ -99,6 +99,24 @@ class ReaderParameters:
     # whose size is not a multiple of the record size (record_length included) is read anyway, its
     # partial last record dropped, instead of being rejected (CobolScanners.scala:86-90)
     debug_ignore_file_size: bool = False
+    # column projection (columns=...): whether the projected plan decodes with the direct kernel
+    # (cbx_plan_options.direct_decode: one lane per record, the requested fields read straight from the
+    # record's bytes) where the plan is eligible.  True / False force the choice; None decides by the
+    # projection's byte share (DIRECT_MAX_SHARE).  A reader without a projection never sets the option.
+    direct_decode: Optional[bool] = None
+
+
+# None-rule of ReaderParameters.direct_decode: the direct kernel is used for a projection whose byte share
+# (projection_share) is at or below this.  None: never -- the kernel stays opt-in (DESIGN.md 5.12 holds the
+# measurements the value comes from).
+DIRECT_MAX_SHARE: Optional[float] = None
+
+
+def projection_share(cb: cbk.Copybook, kept) -> float:
+    """Bytes of the requested fields over the copybook's record size."""
+    from .plan import _iter_prims
+    size = sum(q.data_size * (1 if not q.is_array else q.array_max_size) for q in _iter_prims(cb.ast) if id(q) in kept)
+    return size / max(1, cb.record_size)
 
 
 @dataclass
@@ -321,7 +339,7 @@ class DecodedBatch:
             if isinstance(node, cbk.Group):
                 names, kids = [], []
                 for c in node.children:
-                    if c.is_filler or c.is_child_segment:
+                    if c.is_filler or c.is_child_segment or not plan.keeps(c):
                         continue
                     if isinstance(c, cbk.Group) or c.is_array or plan.field_of_node.get(id(c)) is not None:
                         names.append(c.name)
@@ -363,7 +381,7 @@ class DecodedBatch:
             names.append(nm)
             arrays.append(_file_name_array(v[1], n) if isinstance(v, tuple) else v)
         for g in plan.copybook.ast.children:
-            if not isinstance(g, cbk.Group):
+            if not isinstance(g, cbk.Group) or not plan.keeps(g):
                 continue
             st = build(g, R0, S0, False)
             if self.collapse_root:
@@ -373,6 +391,8 @@ class DecodedBatch:
             else:
                 names.append(g.name)
                 arrays.append(st)
+        if not arrays:   # a projection of no column (count(*)): the row count is all the table holds
+            return pa.table({"_": pa.nulls(n)}).drop_columns(["_"])
         return pa.Table.from_arrays(arrays, names=names)
 
     def _host(self, ci: int) -> Dict[str, Any]:
@@ -422,6 +442,8 @@ class DecodedBatch:
             for c in g.children:
                 if c.is_child_segment:
                     continue   # never in a row (hierarchical children come from `extra`)
+                if not plan.keeps(c):
+                    continue   # column projection: nothing requested below it
                 if c.is_array:
                     ai = plan.array_of_node[id(c)]
                     cci = plan.arrays[ai].count_column
@@ -472,7 +494,8 @@ class DecodedBatch:
         walk = self._row_builder()
         rows = []
         for r in range(self.n_rec):
-            recs = [(g.name, walk(g, r, [])) for g in plan.copybook.ast.children if isinstance(g, cbk.Group)]
+            recs = [(g.name, walk(g, r, [])) for g in plan.copybook.ast.children
+                    if isinstance(g, cbk.Group) and plan.keeps(g)]
             row: Dict[str, Any] = {}
             for nm, v in self.generated(lambda ci: ci):
                 row[nm] = v[1] if isinstance(v, tuple) else self.cell(v, 0, r)
@@ -658,14 +681,14 @@ def parse_copybook_for(copybook_contents: str, params: ReaderParameters) -> cbk.
         debug_fields_policy=params.debug_fields_policy, field_parent_map=params.segment_redefine_parents)
 
 
-def reader_schema(cb: cbk.Copybook, params: ReaderParameters, variable_length: bool):
+def reader_schema(cb: cbk.Copybook, params: ReaderParameters, variable_length: bool, kept=None):
     """The reader's CobolSchema -> createSparkSchema (SC/schema/CobolSchema.scala:77-113): the
     variable-length reader adds File_Id / Record_Id and one Seg_IdN column per segment level
     (CP/reader/VarLenNestedReader.scala:223-225); the fixed-length reader neither."""
     levels = len(params.segment_id_levels) if (variable_length and params.segment_field) else 0
     return spark_schema(cb, params.schema_policy == "collapse_root",
                         params.generate_record_id and variable_length, seg_id_levels=levels,
-                        input_file_name_field=params.input_file_name_column if variable_length else "")
+                        input_file_name_field=params.input_file_name_column if variable_length else "", kept=kept)
 
 
 def hier_root_keys(cb: cbk.Copybook, params: ReaderParameters) -> List[str]:
@@ -861,8 +884,12 @@ class HierBatch:
 class _BaseReader:
     VARIABLE_LENGTH = False
 
-    def __init__(self, copybook_contents: str, params: ReaderParameters):
+    def __init__(self, copybook_contents: str, params: ReaderParameters, columns: Optional[Sequence[str]] = None):
+        """columns: column projection (PrunedFilteredScan.buildScan's requiredColumns) -- field or group
+        names as Copybook.get_field_by_name takes them; the batches hold those fields only (plus the
+        generated columns), in copybook order.  [] is legal (count(*)); None: every field."""
         self.params = params
+        self.columns = None if columns is None else list(columns)
         self.copybook_contents = copybook_contents
         self.copybook = parse_copybook_for(copybook_contents, params)
         var = self.VARIABLE_LENGTH
@@ -871,9 +898,9 @@ class _BaseReader:
         self.hierarchical = var and self.copybook.is_hierarchical
         root_keys = hier_root_keys(self.copybook, params) if self.hierarchical else ()
 
-        def plan(walk: bool):
+        def plan(walk: bool, columns=None, direct: int = 0):
             # the record walk (cbx_walk.h) writes string columns as views
-            return build_plan(self.copybook, segment_field=params.segment_field,
+            return build_plan(self.copybook, columns=columns, direct_decode=direct, segment_field=params.segment_field,
                               segment_redefine_map=params.segment_id_redefine_map or None,
                               generate_record_id=params.generate_record_id and var, window_bytes=params.window_bytes,
                               jit_min_records=params.jit_min_records,
@@ -899,20 +926,35 @@ class _BaseReader:
         if self.hierarchical:
             self.walk_seeds = check_hierarchical(self.copybook, params, self.plan)
         self.native = NativePlan(self.plan)
+        # Column projection: `plan` / `native` stay the FULL plan for everything that reads the record
+        # structure (filters, selection, sparse index, framing by a length field or by variable-size
+        # OCCURS); `out_plan` / `out_native` -- the projected plan -- serve the decode calls and size the
+        # column buffers.  The two share the segment map and the Seg_Id levels, so a selection made with
+        # the full plan decodes with the projected one.  Without a projection they are one object.
+        self.out_plan, self.out_native = self.plan, self.native
+        if self.columns is not None:
+            direct = params.direct_decode
+            if direct is None:
+                from .plan import project_columns
+                direct = DIRECT_MAX_SHARE is not None and \
+                    projection_share(self.copybook, project_columns(self.copybook, self.columns)) <= DIRECT_MAX_SHARE
+            self.out_plan = plan(walk, self.columns, 1 if direct else 0)
+            # a projection of no field at all (count(*) without generated columns) decodes nothing
+            self.out_native = NativePlan(self.out_plan) if self.out_plan.fields else None
 
     @property
     def collapse_root(self) -> bool:
         return self.params.schema_policy == "collapse_root"
 
     def spark_schema(self):
-        return reader_schema(self.copybook, self.params, self.VARIABLE_LENGTH)
+        return reader_schema(self.copybook, self.params, self.VARIABLE_LENGTH, self.out_plan.projected)
 
     def _batch(self, n_rec: int, cols: List[Dict[str, Any]], first_record_id: int, gen_id: bool, stream) -> DecodedBatch:
         """The decoded columns as a batch; with string_utf8 on a record-walk plan (which writes views)
         its string columns are converted to Arrow Utf8 on the device (cbx_views_to_utf8)."""
         if self.walk and self.params.string_utf8:
-            views_to_utf8(self.plan, cols, n_rec, stream)
-        return DecodedBatch(self.plan, n_rec, cols, first_record_id, self.collapse_root, gen_id)
+            views_to_utf8(self.out_plan, cols, n_rec, stream)
+        return DecodedBatch(self.out_plan, n_rec, cols, first_record_id, self.collapse_root, gen_id)
 
     def _empty_selection(self, n: int, device) -> Tuple[Dict[str, Any], N.CbxSelection]:
         """Device arrays of a cbx_selection holding up to n rows."""
@@ -948,19 +990,24 @@ class _BaseReader:
     def _decode_selection(self, d_data, n_bytes: int, sel: Dict[str, Any], gen_id: bool, st) -> DecodedBatch:
         """cbx_decode_selected into column buffers sized by the selection's row count."""
         n_rec = sel["n"]
-        cols, cs = _alloc_columns(self.plan, n_rec, string_capacity(self.native, n_rec), d_data.device)
+        if self.out_native is None:
+            return self._batch(n_rec, [], 0, gen_id, st)
+        nat = self.out_native
+        cols, cs = _alloc_columns(self.out_plan, n_rec, string_capacity(nat, n_rec), d_data.device)
         L = N.load()
-        N.check(L.cbx_decode_selected(self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]),
+        N.check(L.cbx_decode_selected(nat.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]),
                                       n_rec, self.params.start_offset, cs, ctypes.c_void_p(st.cuda_stream)))
-        N.check(L.cbx_plan_check(self.native.handle, ctypes.c_void_p(st.cuda_stream)))
+        N.check(L.cbx_plan_check(nat.handle, ctypes.c_void_p(st.cuda_stream)))
         return self._batch(n_rec, cols, 0, gen_id, st)
 
     def close(self):
         peer = getattr(self, "_peer", None)
         if peer is not None:   # (the pipelined second plan of decode_batches)
-            N.check(N.load().cbx_plan_pipeline(self.native.handle, None, 0, 0))
+            N.check(N.load().cbx_plan_pipeline(self.out_native.handle, None, 0, 0))
             peer.close()
             self._peer = None
+        if self.out_native is not None and self.out_native is not self.native:
+            self.out_native.close()
         self.native.close()
 
 
@@ -1030,15 +1077,18 @@ class FixedLenNestedReader(_BaseReader):
             batch.unhandled_filters = unhandled
             return batch
         exact = None
+        nat = self.out_native
+        if nat is None:
+            return self._batch(n_rec, [], first_record_id, False, st)
         if exact_strings:
-            sizes = (ctypes.c_int64 * self.plan.n_columns)()
-            N.check(L.cbx_string_sizes_fixed(self.native.handle, d_data.data_ptr(), n_rec, stride,
+            sizes = (ctypes.c_int64 * self.out_plan.n_columns)()
+            N.check(L.cbx_string_sizes_fixed(nat.handle, d_data.data_ptr(), n_rec, stride,
                                              self.params.start_offset, sizes, ctypes.c_void_p(st.cuda_stream)))
             exact = list(sizes)
-        cols, cs = _alloc_columns(self.plan, n_rec, string_capacity(self.native, n_rec, exact), d_data.device)
-        N.check(L.cbx_decode_fixed(self.native.handle, d_data.data_ptr(), n_rec, stride, self.params.start_offset,
+        cols, cs = _alloc_columns(self.out_plan, n_rec, string_capacity(nat, n_rec, exact), d_data.device)
+        N.check(L.cbx_decode_fixed(nat.handle, d_data.data_ptr(), n_rec, stride, self.params.start_offset,
                                    first_record_id, cs, ctypes.c_void_p(st.cuda_stream)))
-        N.check(L.cbx_plan_check(self.native.handle, ctypes.c_void_p(st.cuda_stream)))
+        N.check(L.cbx_plan_check(nat.handle, ctypes.c_void_p(st.cuda_stream)))
         return self._batch(n_rec, cols, first_record_id, False, st)
 
     def decode_batches(self, d_data, n_bytes: int, batch_records: int, first_record_id: int = 0) -> List[DecodedBatch]:
@@ -1056,10 +1106,13 @@ class FixedLenNestedReader(_BaseReader):
         L = N.load()
         s0 = torch.cuda.current_stream()
         targets = [(self, s0)]
+        if self.out_native is None:
+            return [self.decode_device(d_data[r0 * stride:], min(bs, n_rec - r0) * stride, first_record_id + r0)
+                    for r0 in range(0, n_rec, bs)]
         if self.params.string_utf8 and not self.walk and n_rec > bs:
             if getattr(self, "_peer", None) is None:
-                self._peer = FixedLenNestedReader(self.copybook_contents, self.params)
-                N.check(L.cbx_plan_pipeline(self.native.handle, self._peer.native.handle, 0, 0))
+                self._peer = FixedLenNestedReader(self.copybook_contents, self.params, self.columns)
+                N.check(L.cbx_plan_pipeline(self.out_native.handle, self._peer.out_native.handle, 0, 0))
             targets.append((self._peer, torch.cuda.Stream(d_data.device)))
             targets[1][1].wait_stream(s0)   # (the data and any earlier work on the first stream)
         out, pending = [], []
@@ -1069,15 +1122,15 @@ class FixedLenNestedReader(_BaseReader):
             with torch.cuda.stream(st):
                 # zero-filled on the stream that decodes the batch: a fill queued on s0 behind the
                 # previous batch's decode is not ordered before the side stream's count and decode
-                cols, cs = _alloc_columns(rd.plan, m, string_capacity(rd.native, m), d_data.device)
+                cols, cs = _alloc_columns(rd.out_plan, m, string_capacity(rd.out_native, m), d_data.device)
             if st is not s0:
                 _record_stream(cols, s0)   # (consumed on s0 after the final wait)
-            N.check(L.cbx_decode_fixed(rd.native.handle, d_data.data_ptr() + r0 * stride, m, stride, self.params.start_offset,
+            N.check(L.cbx_decode_fixed(rd.out_native.handle, d_data.data_ptr() + r0 * stride, m, stride, self.params.start_offset,
                                        first_record_id + r0, cs, ctypes.c_void_p(st.cuda_stream)))
             pending.append((cols, cs))   # (the column table lives until the calls are checked)
             out.append((m, cols, first_record_id + r0, st))
         for rd, st in targets:
-            N.check(L.cbx_plan_check(rd.native.handle, ctypes.c_void_p(st.cuda_stream)))
+            N.check(L.cbx_plan_check(rd.out_native.handle, ctypes.c_void_p(st.cuda_stream)))
         if len(targets) > 1:
             s0.wait_stream(targets[1][1])
         return [self._batch(m, cols, fid, False, st) for m, cols, fid, st in out]
@@ -1355,17 +1408,20 @@ class VarLenNestedReader(_BaseReader):
         n_rec = int(rec_off.numel())
         L = N.load()
         exact = None
+        nat = self.out_native
+        if nat is None:
+            return self._batch(n_rec, [], first_record_id, self.params.generate_record_id, st)
         if exact_strings:
-            sizes = (ctypes.c_int64 * self.plan.n_columns)()
-            N.check(L.cbx_string_sizes_var(self.native.handle, d_data.data_ptr(), n_bytes, rec_off.data_ptr(),
+            sizes = (ctypes.c_int64 * self.out_plan.n_columns)()
+            N.check(L.cbx_string_sizes_var(nat.handle, d_data.data_ptr(), n_bytes, rec_off.data_ptr(),
                                            rec_len.data_ptr(), n_rec, self.params.start_offset, sizes,
                                            ctypes.c_void_p(st.cuda_stream)))
             exact = list(sizes)
-        cols, cs = _alloc_columns(self.plan, n_rec, string_capacity(self.native, n_rec, exact), d_data.device)
-        N.check(L.cbx_decode_var(self.native.handle, d_data.data_ptr(), n_bytes, rec_off.data_ptr(),
+        cols, cs = _alloc_columns(self.out_plan, n_rec, string_capacity(nat, n_rec, exact), d_data.device)
+        N.check(L.cbx_decode_var(nat.handle, d_data.data_ptr(), n_bytes, rec_off.data_ptr(),
                                  rec_len.data_ptr(), n_rec, self.params.start_offset, first_record_id, cs,
                                  ctypes.c_void_p(st.cuda_stream)))
-        N.check(L.cbx_plan_check(self.native.handle, ctypes.c_void_p(st.cuda_stream)))
+        N.check(L.cbx_plan_check(nat.handle, ctypes.c_void_p(st.cuda_stream)))
         return self._batch(n_rec, cols, first_record_id, self.params.generate_record_id, st)
 
     def read_entries(self, d_data, n_bytes: int, entries: Sequence[SparseIndexEntry], entries_per_piece: int = 1,
@@ -1467,6 +1523,9 @@ class VarLenNestedReader(_BaseReader):
         """VarLenHierarchicalIterator over framed records (GPU): cbx_hier_select -> cbx_decode_selected ->
         cbx_hier_list_offsets per child segment.  Index entries are cut at root records, so reading the
         whole stream at once gives the rows (and Record_Ids) of reading entry by entry."""
+        if self.columns is not None:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "columns= on a hierarchical read: the DEPENDING ON resolution "
+                                                  "between the segments of a record indexes the full plan")
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream()
         sp = ctypes.c_void_p(st.cuda_stream)

@@ -47,16 +47,23 @@ class SparkField:
     stype: Tuple[int, int, int] = (0, 0, 0)
 
 
-def _parse_group(g: Group, redefines: List[Group]) -> SparkField:
+def _kept(st: Statement, kept) -> bool:
+    """Column projection: a requested primitive (kept holds their id()s), or a group with one below it."""
+    if isinstance(st, Group):
+        return any(_kept(c, kept) for c in st.children)
+    return id(st) in kept
+
+
+def _parse_group(g: Group, redefines: List[Group], kept=None) -> SparkField:
     """parseGroup (:116-139): child segments are skipped where they sit and appended, as arrays of
     structs, to the group named as their parent (getChildSegments, :175-192)."""
     kids: List[SparkField] = []
     for c in g.children:
-        if c.is_filler:
+        if c.is_filler or (kept is not None and not _kept(c, kept)):
             continue
         if isinstance(c, Group):
             if c.parent_segment is None:
-                kids.append(_parse_group(c, redefines))
+                kids.append(_parse_group(c, redefines, kept))
         else:
             kids.append(SparkField(c.name, "primitive", c, c.is_array, None, spark_type(c)))
     for seg in redefines:
@@ -67,10 +74,13 @@ def _parse_group(g: Group, redefines: List[Group]) -> SparkField:
 
 
 def spark_schema(cb: Copybook, collapse_root: bool, generate_record_id: bool = False,
-                 seg_id_levels: int = 0, input_file_name_field: str = "") -> List[SparkField]:
-    """CobolSchema.createSparkSchema (SC/schema/CobolSchema.scala:77-113)."""
+                 seg_id_levels: int = 0, input_file_name_field: str = "", kept=None) -> List[SparkField]:
+    """CobolSchema.createSparkSchema (SC/schema/CobolSchema.scala:77-113).  kept: a column projection
+    (plan.project_columns) -- the schema of the requested fields and the groups above them; the
+    generated columns stay."""
     redefines = cb.all_segment_redefines()
-    records = [_parse_group(r, redefines) for r in cb.ast.children if isinstance(r, Group)]
+    records = [_parse_group(r, redefines, kept) for r in cb.ast.children
+               if isinstance(r, Group) and (kept is None or _kept(r, kept))]
     fields: List[SparkField] = []
     if collapse_root:
         for r in records:

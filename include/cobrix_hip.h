@@ -43,7 +43,7 @@ typedef __hip_internal::uint64_t uint64_t;
 extern "C" {
 #endif
 
-#define CBX_ABI_VERSION 21
+#define CBX_ABI_VERSION 22
 
 /* status codes */
 #define CBX_OK 0
@@ -172,7 +172,10 @@ typedef struct {
                                specialised for the copybook (compiled once with hipRTC);
                                0 = default (262144), < 0 = never */
     int32_t string_views;   /* string/binary columns in the Arrow string-view layout (below) */
-    int32_t reserved;
+    int32_t direct_decode;  /* 1: decode calls run the direct kernel (one lane per record, every field
+                               read straight from the record's bytes -- for a plan holding a few fields of
+                               a wide record, a column projection) when the plan is eligible
+                               (cbx_plan_direct_eligible), the staged kernels otherwise; 0 = never */
     uint32_t lut[256];      /* code page: UTF-8 bytes (0-23), length (24-25), trimmable (31) */
     cbx_segment_map segments;
 } cbx_plan_options;
@@ -303,9 +306,16 @@ int cbx_plan_kernel_times(cbx_plan* plan, float* decode_ms, float* post_ms, int3
 
 /* Which decode kernel the plan's last decode call ran: *kind = 0 the table-driven kernel,
  * 2 the record walk (cbx_plan_set_walk), 3 its copybook-specialised form,
- * 1 the copybook-specialised kernel.  If specialisation was attempted and failed, *kind = 0 and
- * the reason is in cbx_last_error() (the call itself succeeded on the table-driven kernel). */
+ * 1 the copybook-specialised kernel, 4 the direct kernel (cbx_plan_options.direct_decode).  If
+ * specialisation was attempted and failed, *kind = 0 and the reason is in cbx_last_error() (the call
+ * itself succeeded on the table-driven kernel). */
 int cbx_plan_kernel_kind(cbx_plan* plan, int32_t* kind);
+
+/* Whether decode calls of the plan would run the direct kernel with direct_decode = 1: *eligible = 1,
+ * or 0 with the reason in cbx_last_error().  Eligible: no record walk, no OCCURS array, no list
+ * layout, no Seg_Id level column, string columns absent or in the string-view layout, no pipeline
+ * peer (cbx_plan_pipeline).  An ineligible plan runs the staged kernels; that is not an error. */
+int cbx_plan_direct_eligible(const cbx_plan* plan, int32_t* eligible);
 
 /* Which step the plan's last cbx_frame_var_occurs call walked records with: *kind = 0 the
  * table-driven walk_length, 1 its copybook-specialised form (hipRTC, from jit_min_records records
