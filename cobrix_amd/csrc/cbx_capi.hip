@@ -72,7 +72,9 @@ struct cbx_plan {
     int seg_col = -1;
     int max_pitch = 0;           // widest row of the windowed set
     int n_seq = 0;               // string sequences (column, slot)
-    std::vector<DeferSeq> hdefer;        // deferral sequences (numeric field, slot)
+    std::vector<DeferSeq> hdefer;        // deferral sequences (numeric field, slot), grouped by decoder kind
+    struct DeferGroup { int kind, begin, count; };
+    std::vector<DeferGroup> defer_groups;   // runs of hdefer with one decoder kind: one fixup launch each
     std::vector<int32_t> col_is_string;   // per column: 1 if string/binary
     std::vector<int32_t> col_slots;       // per column: slots
     std::vector<int32_t> col_max_bytes;   // per column: max payload bytes per value
@@ -460,11 +462,28 @@ extern "C" int cbx_plan_create(const cbx_field* fields, int32_t n_fields, const 
             P->col_max_bytes[f.column] = f.size * d.max_utf8;
         } else if ((d.variant == V_ZONED16 || d.variant == V_GENERIC) && !(f.flags & CBX_F_LIST)) {
             d.defer = (int)P->hdefer.size();
-            for (int s = 0; s < d.n_slots; s++) P->hdefer.push_back(DeferSeq{i, s});
+            for (int s = 0; s < d.n_slots; s++) {
+                int eo = d.offset, rem = s;   // the slot's element: row-major over the field's dimensions
+                for (int k = d.n_dims - 1; k >= 0; k--) {
+                    eo += (rem % d.dim_count[k]) * d.dim_stride[k];
+                    rem /= d.dim_count[k];
+                }
+                P->hdefer.push_back(DeferSeq{i, s, (int)P->hdefer.size(), eo});
+            }
         }
         P->dfields_h.push_back(d);
         P->col_is_string[f.column] = is_string_out(f.out_type);
         P->col_slots[f.column] = d.n_slots;
+    }
+    // the fixup pass runs one kernel instantiation per decoder kind: group the sequences by kind
+    // (DeferSeq::seq keeps each one's bitmap row, which the decode kernels index by Field::defer + slot)
+    std::stable_sort(P->hdefer.begin(), P->hdefer.end(), [&](const DeferSeq& x, const DeferSeq& y) {
+        return P->dfields_h[x.field].kind < P->dfields_h[y.field].kind;
+    });
+    for (int i = 0; i < (int)P->hdefer.size(); i++) {
+        const int kind = P->dfields_h[P->hdefer[i].field].kind;
+        if (P->defer_groups.empty() || P->defer_groups.back().kind != kind) P->defer_groups.push_back({kind, i, 0});
+        P->defer_groups.back().count++;
     }
     for (int ai = 0; ai < n_arrays; ai++) {
         const cbx_array& ar = arrays[ai];
@@ -1065,9 +1084,8 @@ static int launch(cbx_plan* P, const CallShape& c, const cbx_column* columns, in
     }
     if (prof) HIP_CHECK(hipEventRecord(ce.e[1], st));
     if (mode == 0 && n_defer > 0) {
-        const unsigned gy = (unsigned)std::min<int64_t>(n_defer, 65535);
-        hipLaunchKernelGGL(fixup_kernel, dim3((unsigned)((n_tiles + 4 * kWave - 1) / (4 * kWave)), gy), dim3(4 * kWave), 0, st, a,
-                           (const CBX_CONST DeferSeq*)P->d_defer, n_defer);
+        for (const cbx_plan::DeferGroup& g : P->defer_groups)   // one launch per decoder kind present
+            fixup_launch(g.kind, a, (const CBX_CONST DeferSeq*)P->d_defer + g.begin, g.count, st);
         HIP_CHECK(hipGetLastError());
     }
     if (P->n_seq > 0 && !((P->view || P->packed) && mode == 0)) {

@@ -390,16 +390,15 @@ CBX_HD Val zoned_finish(const Field& f, bool malformed, int sign, int nd, int nd
     return finalize_decimal(D, ovf, -f.sf + nd, neg, f);
 }
 
-template <typename BP>
-CBX_HD Val decode_zoned(const Field& f, BP p) {
-    const int n = f.size;
+// The scan of decodeEbcdicNumber as a state that takes the field's bytes in order (decode_zoned
+// feeds it from memory, the fixup kernel from a register window).
+struct ZonedScan {
     bool malformed = false;
     int sign = 0;  // 0 none, 1 '+', 2 '-'
     int nd = 0, ndots = 0, after = 0, sig = 0;
-    U128 D = u128(0);
+    U128 D{0, 0};
     bool ovf = false;
-    for (int i = 0; i < n; i++) {
-        uint32_t c = p[i];
+    CBX_HD void step(uint32_t c) {
         uint32_t hi = c >> 4, lo = c & 15;
         bool dig = lo <= 9 && (hi == 0xF || (sign == 0 && (hi == 0xC || hi == 0xD)));
         bool sch = sign == 0 && (c == 0x60 || c == 0x4E);
@@ -418,7 +417,18 @@ CBX_HD Val decode_zoned(const Field& f, BP p) {
         }
         ndots += dot;
     }
-    return zoned_finish(f, malformed, sign, nd, ndots, after, D, ovf);
+};
+
+CBX_HD Val zoned_finish(const Field& f, const ZonedScan& z) {
+    return zoned_finish(f, z.malformed, z.sign, z.nd, z.ndots, z.after, z.D, z.ovf);
+}
+
+template <typename BP>
+CBX_HD Val decode_zoned(const Field& f, BP p) {
+    const int n = f.size;
+    ZonedScan z;
+    for (int i = 0; i < n; i++) z.step(p[i]);
+    return zoned_finish(f, z);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -275,55 +275,146 @@ __global__ __launch_bounds__(kWave * kPlaceWaves) void str_place_kernel(const CB
 // ------------------------------------------------------------------------------------------
 // Fixup: values the fast paths deferred (zoned forms other than F-zone digits + overpunch,
 // wide / P-scaled numerics) are decoded here with the byte-loop decoders, straight from HBM.
-// One thread per (deferral sequence, tile) word of the deferral bitmap; almost all are zero.
+// The deferral bitmap has one word per (deferral sequence, tile); almost all are zero.
 // ------------------------------------------------------------------------------------------
 struct DeferSeq {
     int32_t field, slot;
+    int32_t seq;   // row of the deferral bitmap (Field::defer + slot)
+    int32_t eo;    // byte offset of the element in the record (field offset + the slot's strides)
 };
 
-// One wave per 64 tiles of a deferral sequence: the wave's deferred values (set bits of its 64
-// words, ~0.5 % of the zoned values of SYN200) are enumerated with a wave scan and spread over
-// the lanes one value each, so a word with many deferrals does not serialise its wave.
-__global__ __launch_bounds__(256) void fixup_kernel(KernelArgs a, const CBX_CONST DeferSeq* dseq, int32_t n_defer) {
-    const int lane = threadIdx.x % kWave;
-    const int64_t tile = ((int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave) * kWave + lane;
-    for (int d = blockIdx.y; d < n_defer; d += gridDim.y) {
-        const uint64_t bits = tile < a.n_tiles ? a.defer_bits[(int64_t)d * a.n_tiles + tile] : 0ull;
-        uint32_t total;
-        const uint32_t ex = wave_excl_scan32((uint32_t)__popcll(bits), lane, total);
-        if (total == 0) continue;
-        const DeferSeq ds = ldc(dseq + d);
-        const CBX_CONST Field* fp = a.fields + ds.field;
-        const Field f = ldc(fp);
-        int eo = f.offset, rem = ds.slot;
-        for (int k = f.n_dims - 1; k >= 0; k--) {
-            const int dc = fp->dim_count[k];
-            eo += (rem % dc) * fp->dim_stride[k];
-            rem /= dc;
-        }
-        const DevColumn col = ldc(a.cols + f.column);
-        for (uint32_t j = lane; j < total + (kWave - 1) - ((total + kWave - 1) % kWave); j += kWave) {
-            // owner lane: the last lane whose exclusive prefix is <= j (binary search over the wave)
-            int lo = 0;
+#ifndef CBX_FIX_WORDS   // span A/B: tools/build_variant.py . NAME -DCBX_FIX_WORDS=N
+#define CBX_FIX_WORDS 4
+#endif
+constexpr int kFixThreads = 256;
+constexpr int kFixWords = CBX_FIX_WORDS;            // bitmap words (tiles) per thread
+constexpr int kFixSpan = kFixThreads * kFixWords;   // tiles per workgroup span
+constexpr int kFixList = 4096;                      // entries of the LDS list (one fill)
+static_assert(kFixSpan * kWave <= 65536, "list entries are 16-bit record indices relative to the span");
+
+// Zoned scan of a field of at most 4 * NW bytes from a register window: the aligned dwords that
+// cover the field are loaded up front (one memory wait per value instead of one per byte -- the
+// lanes of a dense pass read 64 different lines, so every byte load is a round trip to L2) and
+// normalised to the field's first byte with v_alignbyte; the scan takes the window's low byte and
+// shifts the window down, so no register is indexed by the loop counter.  A dword that holds no
+// byte of the field is not read (an aligned dword that holds one lies in the field's page).
+template <int NW>
+__device__ __forceinline__ void zoned_scan_window(ZonedScan& z, const CBX_GLOBAL uint8_t* p, int size) {
+    const uint64_t u = (uint64_t)p;
+    const CBX_GLOBAL uint32_t* q = (const CBX_GLOBAL uint32_t*)(u & ~(uint64_t)3);
+    const uint32_t sh = (uint32_t)u & 3u;
+    const uint32_t span = sh + (uint32_t)size;   // bytes from q to the field's end
+    uint32_t d[NW + 1];
 #pragma unroll
-            for (int step = kWave / 2; step >= 1; step >>= 1) {
-                const uint32_t e = (uint32_t)__shfl((int)ex, lo + step, kWave);
-                if (e <= j) lo += step;
-            }
-            // every lane takes part in the shuffles (a shuffle from an inactive lane reads 0)
-            const uint64_t wb = __shfl(bits, lo, kWave);
-            const int64_t wt = __shfl(tile, lo, kWave);
-            const uint32_t we = (uint32_t)__shfl((int)ex, lo, kWave);
-            if (j >= total) continue;
-            uint64_t m = wb;
-            for (uint32_t r = j - we; r > 0; r--) m &= m - 1;   // r-th set bit of the owner's word
-            const int b = __builtin_ctzll(m);
-            const int64_t rec = wt * kWave + b;
-            const int64_t base = a.base_shift + (a.rec_off ? a.rec_off[rec] : rec * (int64_t)a.stride);
-            const Val x = decode_numeric(f, a.data + base + a.start_off + eo);
-            store_value(col, f.out_type, (int64_t)ds.slot * a.pitch + rec, x);
-            if (x.valid) atomicOr((unsigned long long*)(col.validity + (int64_t)ds.slot * a.n_tiles + wt), 1ull << b);
+    for (int i = 0; i <= NW; i++) d[i] = 4u * (uint32_t)i < span ? q[i] : 0u;
+    uint32_t w[NW];
+#pragma unroll
+    for (int i = 0; i < NW; i++) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], sh);
+    for (int i = 0; i < size; i++) {
+        z.step(w[0] & 0xFFu);
+#pragma unroll
+        for (int k = 0; k + 1 < NW; k++) w[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], 1u);
+        w[NW - 1] >>= 8;
+    }
+}
+
+// The byte-loop decoder of one kind (decode_numeric's switch, decided at compile time).  A/B:
+// -DCBX_FIX_NO_WINDOW keeps the zoned byte loads (tools/build_variant.py).
+template <int KIND>
+__device__ __forceinline__ Val decode_kind(const Field& f, const CBX_GLOBAL uint8_t* p) {
+    if constexpr (KIND == CBX_K_BCD) return decode_bcd(f, p);
+    else if constexpr (KIND == CBX_K_BINARY) return decode_binary(f, p);
+    else if constexpr (KIND == CBX_K_ZONED) {
+#ifdef CBX_FIX_NO_WINDOW
+        return decode_zoned(f, p);
+#else
+        ZonedScan z;
+        if (f.size <= 8) zoned_scan_window<2>(z, p, f.size);
+        else if (f.size <= 12) zoned_scan_window<3>(z, p, f.size);
+        else if (f.size <= 20) zoned_scan_window<5>(z, p, f.size);
+        else for (int i = 0; i < f.size; i++) z.step(p[i]);
+        return zoned_finish(f, z);
+#endif
+    } else return decode_ascii_num(f, p);
+}
+
+// One workgroup per span of kFixSpan consecutive tiles of ONE deferral sequence of decoder KIND
+// (field, column and element offset stay wave-uniform).  The span's deferred records (set bits of
+// its words, ~0.5 % of the zoned values of SYN200) are compacted into an LDS list -- popcounts
+// scanned over the workgroup, every thread writes the bit positions of its own words at its
+// prefix -- and the threads then take list entries tid, tid + 256, ...: every pass but the last
+// of a span decodes with all lanes live.  A span with more deferrals than the list holds is
+// processed in successive fills (each thread resumes where its words stopped).
+template <int KIND>
+__global__ __launch_bounds__(kFixThreads) void fixup_kernel(KernelArgs a, const CBX_CONST DeferSeq* dseq, int32_t n_defer) {
+    __shared__ uint16_t s_list[kFixList];
+    __shared__ uint32_t s_wtot[kFixThreads / kWave];
+    const int tid = threadIdx.x, lane = tid % kWave;
+    const int wid = __builtin_amdgcn_readfirstlane(tid / kWave);
+    const int64_t tile0 = (int64_t)blockIdx.x * kFixSpan;
+    for (int d = blockIdx.y; d < n_defer; d += gridDim.y) {
+        if (d != (int)blockIdx.y) __syncthreads();   // the previous sequence's reads of s_wtot / s_list
+        const DeferSeq ds = ldc(dseq + d);
+        const CBX_GLOBAL uint64_t* row = gp(a.defer_bits) + (int64_t)ds.seq * a.n_tiles;
+        uint64_t bits[kFixWords];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int k = 0; k < kFixWords; k++) {   // consecutive threads on consecutive words
+            const int64_t tile = tile0 + k * kFixThreads + tid;
+            bits[k] = tile < a.n_tiles ? row[tile] : 0ull;
+            cnt += (uint32_t)__popcll(bits[k]);
         }
+        uint32_t wtot;
+        uint32_t p = wave_excl_scan32(cnt, lane, wtot);   // position of this thread's first entry
+        if (lane == 0) s_wtot[wid] = wtot;
+        __syncthreads();
+        uint32_t total = 0;
+#pragma unroll
+        for (int i = 0; i < kFixThreads / kWave; i++) {
+            const uint32_t w = s_wtot[i];
+            p += i < wid ? w : 0u;
+            total += w;
+        }
+        if (total == 0) continue;
+        const Field f = ldc(a.fields + ds.field);
+        const DevColumn col = ldc(a.cols + f.column);
+        for (uint32_t base = 0; base < total; base += kFixList) {
+            const uint32_t lim = base + kFixList;
+#pragma unroll
+            for (int k = 0; k < kFixWords; k++) {
+                uint64_t m = bits[k];
+                while (m != 0 && p < lim) {
+                    s_list[p - base] = (uint16_t)((uint32_t)(k * kFixThreads + tid) * kWave + (uint32_t)__builtin_ctzll(m));
+                    m &= m - 1;
+                    p++;
+                }
+                bits[k] = m;
+            }
+            __syncthreads();
+            const uint32_t n = total - base < (uint32_t)kFixList ? total - base : (uint32_t)kFixList;
+            for (uint32_t j = tid; j < n; j += kFixThreads) {
+                const uint32_t e = s_list[j];
+                const int64_t wt = tile0 + (e >> 6);
+                const int b = (int)(e & 63);
+                const int64_t rec = wt * kWave + b;
+                const int64_t rbase = a.base_shift + (a.rec_off ? a.rec_off[rec] : rec * (int64_t)a.stride);
+                const Val x = decode_kind<KIND>(f, gp(a.data) + rbase + a.start_off + ds.eo);
+                store_value(col, f.out_type, (int64_t)ds.slot * a.pitch + rec, x);
+                if (x.valid) atomicOr((unsigned long long*)(col.validity + (int64_t)ds.slot * a.n_tiles + wt), 1ull << b);
+            }
+            if (lim < total) __syncthreads();   // the list is refilled
+        }
+    }
+}
+
+// Launch of the instantiation of one decoder kind over `count` sequences of the (kind-grouped) table.
+static inline void fixup_launch(int kind, const KernelArgs& a, const CBX_CONST DeferSeq* dseq, int32_t count, hipStream_t st) {
+    const dim3 grid((unsigned)((a.n_tiles + kFixSpan - 1) / kFixSpan), (unsigned)(count < 65535 ? count : 65535));
+    switch (kind) {
+    case CBX_K_BCD: hipLaunchKernelGGL(fixup_kernel<CBX_K_BCD>, grid, dim3(kFixThreads), 0, st, a, dseq, count); break;
+    case CBX_K_BINARY: hipLaunchKernelGGL(fixup_kernel<CBX_K_BINARY>, grid, dim3(kFixThreads), 0, st, a, dseq, count); break;
+    case CBX_K_ZONED: hipLaunchKernelGGL(fixup_kernel<CBX_K_ZONED>, grid, dim3(kFixThreads), 0, st, a, dseq, count); break;
+    default: hipLaunchKernelGGL(fixup_kernel<CBX_K_ASCII_NUM>, grid, dim3(kFixThreads), 0, st, a, dseq, count); break;
     }
 }
 

@@ -84,7 +84,8 @@ if dec:
     hi = min(after) if after else float("inf")
     window = {k: (first - 1, last + 1)}
     for x in kernels:
-        if x.startswith(("cbx::list_kernel", "cbx_jit_list", "cbx::fixup_kernel")):   # (the bench's time includes the fixup pass)
+        # (the bench's time includes the fixup pass; its per-kind instantiations trace as "void cbx::fixup_kernel<K>(...)")
+        if x.startswith(("cbx::list_kernel", "cbx_jit_list", "cbx::fixup_kernel", "void cbx::fixup_kernel<")):
             window[x] = (first, hi)
     if "cbx_jit_count" in kernels or bench["config"].get("string_layout", "").startswith("Arrow Utf8"):
         for x in kernels:
