@@ -254,6 +254,13 @@ def _preprocess(contents: str, comments_up_to: int = 6, comments_after: int = 72
     return out
 
 
+# The characters the reference's lexer has a rule for outside string literals (copybookLexer.g4:103-113,
+# 214-232: letters, digits, ':', '-', '_', quotes, ',', '.', '(', ')', '+', '/', the comment's '*', CONTROL_Z).
+# Its lexer reports any other character to a logging listener (ANTLRParser.scala:72-73) and drops it, so
+# a stray one -- the '|' that ends OccursExtractorSpec.scala:37-48's copybook -- separates tokens and no more.
+_LEXER_CHARS = frozenset("ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789:-_'\",.()+/*\x1a")
+
+
 def _tokenize(lines: List[str]) -> List[List[_Tok]]:
     """Split into statements terminated by '.' followed by whitespace/EOF (lexer TERMINAL)."""
     statements: List[List[_Tok]] = []
@@ -272,6 +279,9 @@ def _tokenize(lines: List[str]) -> List[List[_Tok]]:
         if c == "*":  # COMMENT: '*' ~[\r\n]* -> skip
             while i < n and text[i] != "\n":
                 i += 1
+            continue
+        if c not in _LEXER_CHARS:   # no lexer rule starts with it: reported and dropped, the text goes on
+            i += 1
             continue
         if c in "'\"":
             q = c
@@ -295,7 +305,7 @@ def _tokenize(lines: List[str]) -> List[List[_Tok]]:
             i += 1
             continue
         j = i
-        while j < n and text[j] not in " \r\n\f'\"":
+        while j < n and text[j] not in " \r\n\f'\"" and text[j] in _LEXER_CHARS:
             if text[j] == "." and (j + 1 >= n or text[j + 1] in " \r\n\f"):
                 break
             j += 1

@@ -682,11 +682,19 @@ struct RdwStream {
 
 __device__ __forceinline__ void rdw_vmwait(int n) { lds_dma_wait(n); }
 
-// Issue the DMA of window win into its slot (bytes past the input: zeros, range-checked).
+// Bytes of window win the descriptor covers: the input's, rounded up to whole dwords -- the range check
+// drops a dword that crosses the range, and with it the input's last 1-3 bytes (the length bytes of a
+// last header whose 1-3 byte payload ends an input of a size that is no multiple of 4: read as zero, the
+// walk reported a zero-size record).  base is 16-byte aligned, so the dword lies in the input's last page.
+__device__ __forceinline__ int64_t rdw_win_bytes(const RdwStream& s, int64_t a0) {
+    const int64_t left = s.limit - a0;
+    return left < 0 ? 0 : (left > kRdwWin ? kRdwWin : ((left + 3) & ~(int64_t)3));
+}
+
+// Issue the DMA of window win into its slot (dwords past the input: zeros, range-checked).
 __device__ __forceinline__ void rdw_win_dma(const RdwStream& s, int64_t win, int lane) {
     const int64_t a0 = win * kRdwWin;
-    int64_t left = s.limit - a0;
-    left = left < 0 ? 0 : (left > kRdwWin ? kRdwWin : left);
+    const int64_t left = rdw_win_bytes(s, a0);
     const uint64_t b = (uint64_t)(s.base + (a0 < s.limit ? a0 : 0));
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
@@ -703,11 +711,10 @@ __device__ __forceinline__ void rdw_win_dma(const RdwStream& s, int64_t win, int
                  : "=&s"(keep) : "v"(16 * lane), "s"(rs), "s"(dst) : "memory");
 }
 
-// Window win into registers (the speculation's scan): 16 bytes per lane, past the input zeros.
+// Window win into registers (the speculation's scan): 16 bytes per lane, dwords past the input zeros.
 __device__ __forceinline__ uint4 rdw_win_load(const RdwStream& s, int64_t win, int lane) {
     const int64_t a0 = win * kRdwWin;
-    int64_t left = s.limit - a0;
-    left = left < 0 ? 0 : (left > kRdwWin ? kRdwWin : left);
+    const int64_t left = rdw_win_bytes(s, a0);
     const uint64_t b = (uint64_t)(s.base + (a0 < s.limit ? a0 : 0));
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));

@@ -51,6 +51,10 @@ UNSUPPORTED = {
 _CODE_PAGE_CLASSES: Dict[str, List[int]] = {}
 
 
+_FLOATING_POINT_FORMATS = {"ibm": "IBM", "ibm_little_endian": "IBM_LE", "ibm_le": "IBM_LE",
+                           "ieee754": "IEEE754", "ieee754_little_endian": "IEEE754_LE", "ieee754_le": "IEEE754_LE"}
+
+
 class UnsupportedOption(ValueError):
     pass
 
@@ -205,9 +209,12 @@ def parse_options(options: Mapping[str, object]) -> Tuple[ReaderParameters, bool
     trim = opts.get("string_trimming_policy", "both")
     if trim.lower() not in ("none", "left", "right", "both"):
         raise ValueError(f"Invalid value '{trim}' for 'string_trimming_policy' option.")
-    fp = opts.get("floating_point_format", "IBM")
-    if fp.upper() not in ("IBM", "IBM_LE", "IEEE754", "IEEE754_LE"):
-        raise ValueError(f"Invalid value '{fp}' for 'floating_point_format' option.")
+    # FloatingPointFormat.withNameOpt (CP/parser/decoders/FloatingPointFormat.scala:24-42): the enumeration's
+    # names, or -- in any letter case -- ibm, ibm_little_endian, ieee754, ieee754_little_endian
+    fp_in = opts.get("floating_point_format", "IBM")
+    fp = _FLOATING_POINT_FORMATS.get(fp_in.lower())
+    if fp is None:
+        raise ValueError(f"Invalid value '{fp_in}' for 'floating_point_format' option.")
     debug = opts.get("debug", "false").lower()
     debug_policy = {"false": "none", "none": "none", "true": "hex", "hex": "hex", "raw": "raw"}.get(debug)
     if debug_policy is None:
@@ -230,7 +237,7 @@ def parse_options(options: Mapping[str, object]) -> Tuple[ReaderParameters, bool
         is_ebcdic=is_ebcdic,
         ebcdic_code_page=opts.get("ebcdic_code_page", "common"),
         ebcdic_code_page_table=code_page_table,
-        floating_point_format=fp.upper(),
+        floating_point_format=fp,
         is_utf16_big_endian=_bool(opts.get("is_utf16_big_endian", "true"), "is_utf16_big_endian"),
         ascii_charset=opts.get("ascii_charset", ""),
         variable_size_occurs=_bool(opts.get("variable_size_occurs", "false"), "variable_size_occurs") if var_len else False,

@@ -548,6 +548,9 @@ def hier_rows(cb: cbk.Copybook, data: bytes, p, file_id: int = 0,
     red = p.segment_id_redefine_map
     roots = set(root_segment_ids(cb, p))
     ast = O.OracleAst(cb)
+    # extractHierarchicalRecord's variableLengthOccurs (RecordExtractors.scala:214, 229-277): arrays step
+    # by their walked size, as on the flat path (var_len_rows)
+    ast.opts.variable_size_occurs = int(p.variable_size_occurs)
     tb = _hier_tables(cb, ast)
     group_node = {g.name: ast.node_of(g) for g in cb.all_segment_redefines()}
     keys: Dict[str, int] = {}

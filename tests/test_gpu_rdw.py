@@ -159,6 +159,22 @@ def test_truncated_last_record_and_tiny_inputs():
         assert np.array_equal(off, eo) and np.array_equal(ln, el), cut
 
 
+@pytest.mark.parametrize("big_endian", [False, True])
+@pytest.mark.parametrize("tail", [1, 2, 3, 4, 5])
+@pytest.mark.parametrize("lead", [0, 1, 2, 3])
+def test_last_header_in_the_inputs_last_partial_dword(lead, tail, big_endian):
+    """A dense file (the wave walk: more than 256 short records) whose last record's payload is 1-5 bytes,
+    at every size modulo 4: the last header's length bytes then share an aligned dword with the end of
+    the input, which the ring's range-checked loads once dropped (read as a zero-size record)."""
+    def rec(n):
+        return (bytes([n >> 8, n & 0xFF, 0, 0]) if big_endian else bytes([0, 0, n & 0xFF, n >> 8])) + bytes([0xF1] * n)
+    raw = rec(7 + lead) + rec(5) * 400 + rec(tail)
+    eo, el = _oracle(raw, big_endian=big_endian)
+    assert len(eo) == 402 and el[-1] == tail and eo[-1] + tail == len(raw)
+    off, ln = _frame(raw, is_rdw_big_endian=big_endian)
+    assert np.array_equal(off, eo) and np.array_equal(ln, el)
+
+
 @pytest.mark.parametrize("chunk", [16, None])
 def test_zero_length_header_is_an_error_at_the_first_occurrence(monkeypatch, chunk):
     if chunk:

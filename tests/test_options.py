@@ -75,6 +75,25 @@ def test_input_file_name_schema_position():
         assert names.index("F") == pos
 
 
+@pytest.mark.parametrize("name,fmt", [
+    ("IBM", "IBM"), ("ibm", "IBM"), ("IBM_little_endian", "IBM_LE"), ("ibm_LITTLE_endian", "IBM_LE"),
+    ("IBM_LE", "IBM_LE"), ("IEEE754", "IEEE754"), ("ieee754", "IEEE754"),
+    ("IEEE754_little_endian", "IEEE754_LE"), ("ieee754_Little_Endian", "IEEE754_LE"), ("IEEE754_LE", "IEEE754_LE")])
+def test_floating_point_format_names(name, fmt):
+    """FloatingPointFormat.withNameOpt (CP/parser/decoders/FloatingPointFormat.scala:24-42): the four
+    spellings the reference takes in any letter case (Test03IbmFloats.scala:127, 163), and the
+    enumeration's own names."""
+    p, _ = parse_options({"floating_point_format": name})
+    assert p.floating_point_format == fmt
+    assert parse_copybook_for("       01  R.\n          05  F  COMP-1.\n", p).floating_point_format == fmt
+
+
+def test_floating_point_format_unknown_name():
+    for bad in ("IBM_big_endian", "IEEE", "little_endian", ""):
+        with pytest.raises(ValueError, match="for 'floating_point_format' option"):
+            parse_options({"floating_point_format": bad})
+
+
 def test_segment_children_with_levels():
     with pytest.raises(ValueError, match="cannot be used with 'segment_id_level\\*' or 'segment_id_root'"):
         parse_options({"is_record_sequence": "true", "segment_field": "S", "segment_id_level0": "1",
