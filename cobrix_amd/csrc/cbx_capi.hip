@@ -128,6 +128,7 @@ struct cbx_plan {
     int rec_extent = 0;          // bytes past the decode base that any field (any OCCURS element) reaches
     std::string jit_error;
     int last_kind = 0;
+    cbx_launch_info last_info{};   // cbx_plan_launch_info: how launch() ran the last decode call
     int32_t* d_status = nullptr;
     int num_cus = 256;
     // record walk (cbx_plan_set_walk, cbx_walk.h)
@@ -1047,6 +1048,22 @@ static int launch(cbx_plan* P, const CallShape& c, const cbx_column* columns, in
         if ((r = string_scan(P, n_tiles, st))) return r;
         if (piped) HIP_CHECK(hipEventRecord(P->pipe_done, st));
     }
+    if (mode == 0) {   // cbx_plan_launch_info (the count pass's own mode-1 call leaves it alone)
+        cbx_launch_info li{};
+        li.kind = P->last_kind;
+        li.staging = span ? 2 : contig ? 1 : 0;
+        li.coop = coop ? 1 : 0;
+        li.kp = contig ? contig_kp(sdw) : span ? span_kp : 0;
+        li.padded_rows = contig && a.cpitch != c.stride ? 1 : 0;
+        li.n_windows = (int32_t)S.win.size();
+        for (const Window& w : S.win)
+            if (w.global && (w.nop_end > w.nop_begin || w.sop_end > w.sop_begin)) li.global_window = 1;
+        li.count_kernel = !(P->packed && P->n_seq > 0) ? 0 : cfn ? 1 : 2;
+        li.base_shift = (int32_t)a.base_shift;
+        li.grid = grid;
+        li.blocks_needed = blocks_needed;
+        P->last_info = li;
+    }
     if (jfn) {
         void* kargs[] = {&a};
         HIP_CHECK(hipModuleLaunchKernel(jfn, (unsigned)grid, 1, 1, kWave * kWavesPerBlock, 1, 1, (unsigned)lds, st, kargs, nullptr));
@@ -1440,6 +1457,7 @@ static int walk_launch(cbx_plan* P, const CallShape& c, cbx_column* columns, hip
         P->ev_calls.push_back(ce);
     }
     P->last_kind = jfn ? 3 : 2;
+    P->last_info = cbx_launch_info{};
     return CBX_OK;
 }
 
@@ -1455,6 +1473,7 @@ static std::string direct_refusal(const cbx_plan* P) {
 static int gather_launch(cbx_plan* P, const CallShape& c, const cbx_column* columns, hipStream_t st) {
     const int64_t n_tiles = (c.n_rec + kWave - 1) / kWave;
     P->last_kind = 4;
+    P->last_info = cbx_launch_info{};
     if (n_tiles == 0) return CBX_OK;
     P->h_cols.resize(P->n_columns);
     P->h_view_geo.assign(2 * (size_t)P->n_columns, 0);
@@ -1661,6 +1680,13 @@ extern "C" int cbx_plan_kernel_kind(cbx_plan* P, int32_t* kind) {
     if (!P || !kind) return fail(CBX_E_ARGUMENT, "cbx_plan_kernel_kind: invalid arguments");
     *kind = P->last_kind;
     if (!P->last_kind && !P->jit_error.empty()) g_err = P->jit_error;
+    return CBX_OK;
+}
+
+extern "C" int cbx_plan_launch_info(cbx_plan* P, cbx_launch_info* out) {
+    if (!P || !out) return fail(CBX_E_ARGUMENT, "cbx_plan_launch_info: invalid arguments");
+    *out = P->last_info;
+    out->kind = P->last_kind;
     return CBX_OK;
 }
 

@@ -1755,11 +1755,12 @@ __device__ __forceinline__ void decode_window(const KernelArgs& a, const Window&
 // wave-instruction) and written to LDS rows of cpitch bytes (odd dword count when padding pays).
 // The loads of tile t + stride are issued before tile t is decoded, KP per lane, ALL of them
 // unconditionally through a range-checked buffer descriptor over [a0, end of input): chunks past
-// the span get an out-of-range offset (no memory access, zero data), and nothing past the input
-// is read.  The range check is per dword (a chunk straddling the end of the input returns its
-// in-range dwords), and the records end on a dword boundary (stride and base are multiples of 4),
-// so every byte of the last tile arrives -- tests/test_gpu_parity.py decodes batches whose input
-// ends 8 bytes into a chunk.  Loads
+// the span get an out-of-range offset (no memory access, zero data), and nothing past the dword
+// that holds the input's last byte is read.  The range check is per dword (a chunk straddling the
+// end of the input returns its in-range dwords); fixed-length records end on a dword boundary (stride
+// and base are multiples of 4), variable-length input need not, so the range is rounded up to whole
+// dwords -- every byte of the last tile arrives: tests/test_gpu_parity.py decodes batches whose input
+// ends 8 bytes into a chunk, tests/test_gpu_staging.py RDW files that end 1-3 bytes into a dword.  Loads
 // that are always issued and always overwrite the same registers leave the compiler no reason to
 // copy the buffer (a copy would wait for the loads, the whole prefetch) anywhere in the loop.
 // KP: chunks per lane -- exact for the specialised kernel (ceil(chunks per span / 64)), the plan
@@ -1802,7 +1803,10 @@ __device__ __forceinline__ ContigSpan contig_span(const KernelArgs& a, int64_t t
 // provably uniform (readfirstlane), so no waterfall loop wraps the loads.
 template <int KP>
 __device__ __forceinline__ void contig_issue(const KernelArgs& a, const ContigSpan& sp, int lane, uint4 (&buf)[KP]) {
-    int64_t left = a.data_len - sp.a0;
+    // the range in whole dwords: the check is per dword, and variable-length input (span_loop) may end
+    // inside one -- a dword cut by the range would read as zero, its in-range bytes with it.  a0 is
+    // 16-byte aligned, so the rounded range ends inside the aligned dword that holds the last input byte
+    int64_t left = (a.data_len - sp.a0 + 3) & ~(int64_t)3;
     left = left < 0 ? 0 : (left > (1 << 20) ? (1 << 20) : left);
     const uint64_t base = (uint64_t)(a.data + sp.a0);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);

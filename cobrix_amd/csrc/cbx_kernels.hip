@@ -85,7 +85,8 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void decode_kernel(KernelAr
             const Window w = ldc(a.windows + wi);
             if (a.mode == 1 && w.sop_begin == w.sop_end) continue;
             if (w.global) {
-                decode_window<true>(a, w, t, rp, 0u, l.cnt, l.lut, l.str, lane);
+                // (the decode base: fields lie start_off bytes into the record, as in a staged image)
+                decode_window<true>(a, w, t, rp, (uint32_t)a.start_off, l.cnt, l.lut, l.str, lane);
                 continue;
             }
             const uint32_t rec_addr = stage_window(a, w, t, l.img, lane);

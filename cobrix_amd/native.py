@@ -44,8 +44,8 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_hier_list_offsets", "cbx_plan_set_walk", "cbx_frame_var_occurs",
                     "cbx_plan_set_record_base", "cbx_frame_length_field", "cbx_plan_set_odo_counts",
                     "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline",
-                    "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible")
-ABI_VERSION = 22
+                    "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info")
+ABI_VERSION = 23
 
 
 class NativeLibraryError(RuntimeError):
@@ -202,6 +202,22 @@ class CbxHierWalk(ctypes.Structure):
                 ("seeds", ctypes.c_void_p)]
 
 
+STAGING_WINDOWED, STAGING_CONTIGUOUS, STAGING_SPAN = 0, 1, 2
+
+
+class CbxLaunchInfo(ctypes.Structure):
+    """cbx_plan_launch_info: how the plan's last decode call launched its decode kernel."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "staging", "coop", "kp", "padded_rows", "n_windows",
+                                                "global_window", "count_kernel", "base_shift", "reserved")] + \
+               [("grid", ctypes.c_int64), ("blocks_needed", ctypes.c_int64)]
+
+
+def launch_info(plan_handle) -> CbxLaunchInfo:
+    info = CbxLaunchInfo()
+    check(load().cbx_plan_launch_info(plan_handle, ctypes.byref(info)))
+    return info
+
+
 _lib = None
 
 
@@ -259,7 +275,8 @@ def load():
                      ("cbx_plan_pipeline", [P, P, i32, i32]),
                      ("cbx_filter_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, P]),
                      ("cbx_filter_pass_times", [P, P, P, P]),
-                     ("cbx_plan_direct_eligible", [P, P])):
+                     ("cbx_plan_direct_eligible", [P, P]),
+                     ("cbx_plan_launch_info", [P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):

@@ -43,7 +43,7 @@ typedef __hip_internal::uint64_t uint64_t;
 extern "C" {
 #endif
 
-#define CBX_ABI_VERSION 22
+#define CBX_ABI_VERSION 23
 
 /* status codes */
 #define CBX_OK 0
@@ -310,6 +310,25 @@ int cbx_plan_kernel_times(cbx_plan* plan, float* decode_ms, float* post_ms, int3
  * specialisation was attempted and failed, *kind = 0 and the reason is in cbx_last_error() (the call
  * itself succeeded on the table-driven kernel). */
 int cbx_plan_kernel_kind(cbx_plan* plan, int32_t* kind);
+
+/* How the plan's last decode call launched its decode kernel: the kernel kind, the way a tile's
+ * records were staged into LDS and the launch geometry (read-only; tests pin the dispatch with it).
+ * The staging fields describe the staged kernels (kind 0 / 1); the record walk and the direct kernel
+ * (kind 2 / 3 / 4) report the kind alone, the other fields zero. */
+typedef struct cbx_launch_info {
+    int32_t kind;          /* as cbx_plan_kernel_kind */
+    int32_t staging;       /* 0 windowed, 1 contiguous, 2 span */
+    int32_t coop;          /* cooperative tiles: one tile per workgroup */
+    int32_t kp;            /* 16-byte chunks per lane (contiguous / span), else 0 */
+    int32_t padded_rows;   /* contiguous: LDS rows padded to an odd dword pitch (pitch != stride) */
+    int32_t n_windows;     /* windows of the op set used */
+    int32_t global_window; /* the op set has a global (HBM) window with fields in it */
+    int32_t count_kernel;  /* Utf8 count pass: 0 none, 1 specialised, 2 table-driven mode 1 */
+    int32_t base_shift;    /* data pointer & 15 */
+    int32_t reserved;
+    int64_t grid, blocks_needed;   /* workgroups launched / workgroups that cover every tile once */
+} cbx_launch_info;
+int cbx_plan_launch_info(cbx_plan* plan, cbx_launch_info* out);
 
 /* Whether decode calls of the plan would run the direct kernel with direct_decode = 1: *eligible = 1,
  * or 0 with the reason in cbx_last_error().  Eligible: no record walk, no OCCURS array, no list
