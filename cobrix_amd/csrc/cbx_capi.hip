@@ -27,6 +27,7 @@
 #include "cbx_walk.h"
 #include "cbx_chain.h"
 #include "cbx_filter.h"
+#include "cbx_aggregate.h"
 #include "cbx_gather.h"
 
 using namespace cbx;
@@ -170,6 +171,7 @@ struct cbx_plan {
     struct CallEvents { hipEvent_t e[3]; };
     std::vector<CallEvents> ev_calls;    // recorded, not yet read
     float flt_ms[3] = {0.f, 0.f, 0.f};   // test / scan / emit of the last cbx_filter_records call (profiling)
+    float agg_ms[2] = {0.f, 0.f};        // accumulate / combine of the last cbx_aggregate_records call (profiling)
     // the direct projected decode (cbx_gather.h; cbx_plan_options.direct_decode)
     bool direct_ok = false;              // the plan's shape is one the direct kernel decodes
     std::string direct_why;              // why not
@@ -2400,6 +2402,87 @@ extern "C" int cbx_filter_pass_times(cbx_plan* P, float* test_ms, float* scan_ms
     if (test_ms) *test_ms = P->flt_ms[0];
     if (scan_ms) *scan_ms = P->flt_ms[1];
     if (emit_ms) *emit_ms = P->flt_ms[2];
+    return CBX_OK;
+}
+
+// Aggregate pushdown (cbx_aggregate.h): accumulate (grid-stride, one slab per workgroup) -> combine.
+extern "C" int cbx_aggregate_records(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                     const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                     int32_t start_offset, const cbx_filter* filter, const cbx_aggregate* aggregate,
+                                     int32_t max_workgroups, cbx_aggregate_result* result, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !aggregate || !result || n_rec < 0 || n_bytes < 0 || start_offset < 0 || max_workgroups < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_records: invalid arguments");
+    memset(result, 0, sizeof(*result));
+    P->agg_ms[0] = P->agg_ms[1] = 0.f;
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_records: exactly one source (selection, framed records, record stride)");
+    struct Progs { AggProg agg; FilterProg flt; };
+    std::vector<Progs> progs(1);
+    std::string err;
+    int rb = aggregate_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, aggregate, &progs[0].agg, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    if (filter) {
+        rb = filter_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, filter, &progs[0].flt, err);
+        if (rb != CBX_OK) return fail(rb, err);
+    }
+    if (n_rec == 0) return CBX_OK;
+    if (!d_data || (in && (!in->rec_off || !in->rec_len || !in->segment)))
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_records: data and selection arrays required");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_records: n_rec records of rec_stride bytes exceed n_bytes");
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    int64_t grid = std::min<int64_t>((n_tiles + kAggWaves - 1) / kAggWaves, (int64_t)P->num_cus * 8);
+    if (max_workgroups > 0) grid = std::min<int64_t>(grid, max_workgroups);
+    // block: programs | slabs (grid) | result
+    const size_t o_slab = (sizeof(Progs) + 15) & ~(size_t)15;
+    const size_t o_res = o_slab + sizeof(cbx_aggregate_result) * (size_t)grid;
+    AsyncBlock blk(st);
+    HIP_CHECK(hipMallocAsync(&blk.p, o_res + sizeof(cbx_aggregate_result), st));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    HIP_CHECK(hipMemcpyAsync(b8, progs.data(), filter ? sizeof(Progs) : sizeof(AggProg), hipMemcpyHostToDevice, st));
+    AggArgs g{};
+    FilterArgs& a = g.src;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = filter ? (const CBX_CONST FilterProg*)(b8 + offsetof(Progs, flt)) : nullptr;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    g.agg = (const CBX_CONST AggProg*)b8;
+    g.has_filter = filter ? 1 : 0;
+    g.slabs = (cbx_aggregate_result*)(b8 + o_slab);
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    hipEvent_t* ev = pe.e;
+    if (P->profiling) {
+        for (int k = 0; k < 3; k++) if (!(ev[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    hipLaunchKernelGGL(aggregate_kernel, dim3((unsigned)grid), dim3(kAggThreads), 0, st, g);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    hipLaunchKernelGGL(aggregate_combine_kernel, dim3(1), dim3(kAggCombineThreads), 0, st,
+                       (const cbx_aggregate_result*)g.slabs, (int32_t)grid, (cbx_aggregate_result*)(b8 + o_res));
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(result, b8 + o_res, sizeof(cbx_aggregate_result), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (P->profiling)
+        for (int k = 0; k < 2; k++) HIP_CHECK(hipEventElapsedTime(&P->agg_ms[k], ev[k], ev[k + 1]));
+    return CBX_OK;
+}
+
+extern "C" int cbx_aggregate_pass_times(cbx_plan* P, float* accumulate_ms, float* combine_ms) {
+    if (!P) return fail(CBX_E_ARGUMENT, "null plan");
+    if (accumulate_ms) *accumulate_ms = P->agg_ms[0];
+    if (combine_ms) *combine_ms = P->agg_ms[1];
     return CBX_OK;
 }
 

@@ -44,8 +44,9 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_hier_list_offsets", "cbx_plan_set_walk", "cbx_frame_var_occurs",
                     "cbx_plan_set_record_base", "cbx_frame_length_field", "cbx_plan_set_odo_counts",
                     "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline",
-                    "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info")
-ABI_VERSION = 23
+                    "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info",
+                    "cbx_aggregate_records", "cbx_aggregate_pass_times")
+ABI_VERSION = 24
 
 
 class NativeLibraryError(RuntimeError):
@@ -151,6 +152,29 @@ class CbxFilter(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("terms", CbxFilterTerm * CBX_FILTER_MAX_TERMS),
                 ("literals", CbxFilterLiteral * CBX_FILTER_MAX_LITERALS),
                 ("pool", ctypes.c_uint8 * CBX_FILTER_POOL_BYTES)]
+
+
+# aggregate pushdown (cbx_aggregate): function bits, table limit
+AGG_COUNT, AGG_MIN, AGG_MAX, AGG_SUM = 1, 2, 4, 8
+CBX_AGG_MAX_TERMS = 16
+
+
+class CbxAggregateTerm(ctypes.Structure):
+    _fields_ = [("field", ctypes.c_int32), ("funcs", ctypes.c_int32)]
+
+
+class CbxAggregate(ctypes.Structure):
+    _fields_ = [("n_terms", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("terms", CbxAggregateTerm * CBX_AGG_MAX_TERMS)]
+
+
+class CbxAggregateValue(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_int64), ("min_lo", ctypes.c_uint64), ("min_hi", ctypes.c_uint64),
+                ("max_lo", ctypes.c_uint64), ("max_hi", ctypes.c_uint64), ("sum", ctypes.c_uint64 * 3)]
+
+
+class CbxAggregateResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int64), ("values", CbxAggregateValue * CBX_AGG_MAX_TERMS)]
 
 
 W_GROUP, W_PRIM = 0, 1
@@ -276,7 +300,9 @@ def load():
                      ("cbx_filter_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, P]),
                      ("cbx_filter_pass_times", [P, P, P, P]),
                      ("cbx_plan_direct_eligible", [P, P]),
-                     ("cbx_plan_launch_info", [P, P])):
+                     ("cbx_plan_launch_info", [P, P]),
+                     ("cbx_aggregate_records", [P, P, i64, P, P, P, i64, i32, i32, P, P, i32, P, P]),
+                     ("cbx_aggregate_pass_times", [P, P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):

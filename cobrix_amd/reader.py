@@ -21,6 +21,8 @@ import numpy as np
 
 from . import copybook as cbk
 from . import native as N
+from .aggregate import AggregateResult, compile_aggregates
+from .aggregate import Unhandled as AggregateUnhandled
 from .filter import compile_filters
 from .plan import DecodePlan, NativePlan, NeedsWalk, build_plan
 from .schema import ST_DECIMAL, spark_schema
@@ -987,6 +989,31 @@ class _BaseReader:
         out["source"] = sel   # (the input selection's arrays stay alive with the result)
         return out
 
+    def _aggregate_records(self, aggregates, filters, d_data, n_bytes: int, n_rec: int, st, *, sel=None, rec_off=None,
+                           rec_len=None, stride: int = 0, max_workgroups: int = 0) -> AggregateResult:
+        """cbx_aggregate_records over one source (a selection, framed records, fixed-length records) through
+        the full plan.  All or nothing: raises `cobrix_amd.aggregate.Unhandled` when a function cannot be
+        pushed, or when a filter cannot be compiled (an aggregate over unfiltered rows would be wrong)."""
+        table, slots = compile_aggregates(self.plan, aggregates)
+        flt = None
+        if filters:
+            flt, unhandled = compile_filters(self.plan, filters)
+            if unhandled:
+                raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        res = N.CbxAggregateResult()
+        N.check(N.load().cbx_aggregate_records(
+            self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+            rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+            n_rec, stride, self.params.start_offset, ctypes.byref(flt) if flt is not None else None,
+            ctypes.byref(table), max_workgroups, ctypes.byref(res), ctypes.c_void_p(st.cuda_stream)))
+        return AggregateResult.from_struct(table, slots, res)
+
+    def aggregate_pass_times(self) -> Tuple[float, float]:
+        """(accumulate, combine) ms of the last aggregate call (cbx_plan_set_profiling on; zeros otherwise)."""
+        a, c = ctypes.c_float(0), ctypes.c_float(0)
+        N.check(N.load().cbx_aggregate_pass_times(self.native.handle, ctypes.byref(a), ctypes.byref(c)))
+        return a.value, c.value
+
     def _decode_selection(self, d_data, n_bytes: int, sel: Dict[str, Any], gen_id: bool, st) -> DecodedBatch:
         """cbx_decode_selected into column buffers sized by the selection's row count."""
         n_rec = sel["n"]
@@ -1140,6 +1167,28 @@ class FixedLenNestedReader(_BaseReader):
         self.check_binary_data_validity(len(data))
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
         return self.decode_device(t, len(data), first_record_id, filters=filters)
+
+    def aggregate_device(self, d_data, n_bytes: int, aggregates, filters=None, stream=None,
+                         max_workgroups: int = 0) -> AggregateResult:
+        """Aggregate pushdown over a split resident in HBM (`cobrix_amd.aggregate` functions, SupportsPushDown-
+        Aggregates.pushAggregation): COUNT(*), COUNT, MIN, MAX and SUM over the rows `decode_device(...,
+        filters=filters)` would return, computed from the record bytes by cbx_aggregate_records -- no selection
+        and no column is written.  Raises `cobrix_amd.aggregate.Unhandled` (with the reason) when a function or
+        a filter cannot be evaluated exactly on the GPU: nothing is computed in part.
+        max_workgroups: a bound on the accumulate pass's grid for a caller that shares the device (0: the
+        library's choice); the result does not depend on it."""
+        torch = _torch()
+        stride = self.get_record_size()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        return self._aggregate_records(aggregates, filters, d_data, n_bytes, n_bytes // stride, st, stride=stride,
+                                       max_workgroups=max_workgroups)
+
+    def aggregate(self, data: bytes, aggregates, filters=None) -> AggregateResult:
+        """`aggregate_device` over host bytes, with the file-size checks of `decode`."""
+        torch = _torch()
+        self.check_binary_data_validity(len(data))
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        return self.aggregate_device(t, len(data), aggregates, filters)
 
     def get_row_iterator(self, data: bytes) -> Iterator[dict]:
         return iter(self.decode(data).to_rows())
@@ -1873,6 +1922,39 @@ class VarLenNestedReader(_BaseReader):
             return self._file_column(self.decode_device(t, vb, off, ln, first_record_id), input_file_name)
         off, ln = self.frame(t, len(data), seeds) if self.params.is_record_sequence else self.frame_fixed(t, len(data))
         return self._file_column(self.decode_device(t, len(data), off, ln, first_record_id), input_file_name)
+
+    def aggregate_device(self, d_data, n_bytes: int, sel_or_framing, aggregates, filters=None, stream=None,
+                         max_workgroups: int = 0) -> AggregateResult:
+        """Aggregate pushdown (`cobrix_amd.aggregate` functions) over a selection (`select`'s result: the rows
+        `decode_selected` would return, after segment_filter, the file footer and the sparse-index entries)
+        or over framed records ((rec_off, rec_len): the rows `decode_device` would return), restricted to the
+        rows `filters` keep.  The active segment comes from the selection or from the plan's segment map; a
+        reader with segment id levels aggregates framed records too (no Seg_Id state is needed).  Raises
+        `cobrix_amd.aggregate.Unhandled` when a function or a filter cannot be evaluated exactly on the GPU.
+        Results of several calls (batches, index entries, shards) combine with `AggregateResult.merge`."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "aggregates on a hierarchical read: rows are trees of segments")
+        if isinstance(sel_or_framing, dict):
+            return self._aggregate_records(aggregates, filters, d_data, n_bytes, sel_or_framing["n"], st,
+                                           sel=sel_or_framing, max_workgroups=max_workgroups)
+        rec_off, rec_len = sel_or_framing
+        return self._aggregate_records(aggregates, filters, d_data, n_bytes, int(rec_off.numel()), st, rec_off=rec_off,
+                                       rec_len=rec_len, max_workgroups=max_workgroups)
+
+    def aggregate(self, data: bytes, aggregates, filters=None, file_id: int = 0) -> AggregateResult:
+        """Aggregate pushdown over a whole file: the rows `read(data, filters=filters)` would return (framing,
+        sparse index, selection with segment_filter and file_end_offset, then the filters)."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "aggregates on a hierarchical read: rows are trees of segments")
+        t = self._device_file(data)
+        off, ln, vb = self.frame_file(t, len(data))
+        entries = None
+        if self.index_generation_needed() and not self.params.is_text:
+            entries = self.generate_index(t, len(data), off, ln, file_id)
+        sel = self.select(t, vb, off, ln, entries, file_id)
+        return self.aggregate_device(t, vb, sel, aggregates, filters)
 
     def get_row_iterator(self, data: bytes) -> Iterator[dict]:
         return iter(self.read(data).to_rows())

@@ -43,7 +43,7 @@ typedef __hip_internal::uint64_t uint64_t;
 extern "C" {
 #endif
 
-#define CBX_ABI_VERSION 23
+#define CBX_ABI_VERSION 24
 
 /* status codes */
 #define CBX_OK 0
@@ -516,6 +516,68 @@ int cbx_filter_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, c
 /* Durations in ms of the three passes of the plan's last cbx_filter_records call, measured with HIP
  * events on its stream while cbx_plan_set_profiling is on (zeros otherwise). */
 int cbx_filter_pass_times(cbx_plan* plan, float* test_ms, float* scan_ms, float* emit_ms);
+
+/* ---- aggregate pushdown ----
+ *
+ * What Spark's SupportsPushDownAggregates.pushAggregation hands a data source: COUNT(*), COUNT(col),
+ * MIN, MAX and SUM over the rows a filter keeps, computed from the records' bytes -- no selection and no
+ * column is written.  cbx_aggregate lists up to CBX_AGG_MAX_TERMS terms, each one field of the plan's
+ * cbx_field table with a bit mask of functions (a field is decoded once however many functions are
+ * asked of it; a field appears in one term only; an empty table is COUNT(*) alone).
+ * The value aggregated is exactly the one the filter compares: null where the decode makes the field
+ * null (a malformed value, a numeric reaching past the record's end, a field of a segment redefine that
+ * is not the record's active segment, a string starting past the record's end), else the column's
+ * output value (int32 / int64 / the unscaled decimal at the Spark scale) as a signed 128-bit number.
+ * Nulls are skipped, as SQL aggregates skip them.
+ * Result: n_rows is the number of records the filter keeps (COUNT(*)); per term `count` is the number
+ * of non-null values of its field (kept whatever the mask), min / max are 128-bit two's complement and
+ * sum is 192-bit two's complement in three little-endian limbs -- |value| < 2^127 and fewer than 2^63
+ * records, so the sum is exact and does not depend on the order of addition.  min, max and sum are
+ * meaningful only when count > 0 and their function was asked for, and are zero otherwise.  Two
+ * results over disjoint records merge by adding n_rows, count and sum and taking the smaller min /
+ * larger max of the sides with count > 0. */
+#define CBX_AGG_MAX_TERMS 16
+enum cbx_aggregate_func { CBX_AGG_COUNT = 1, CBX_AGG_MIN = 2, CBX_AGG_MAX = 4, CBX_AGG_SUM = 8 };
+typedef struct {
+    int32_t field;         /* index into the plan's cbx_field table */
+    int32_t funcs;         /* cbx_aggregate_func bits, not empty */
+} cbx_aggregate_term;
+typedef struct {
+    int32_t n_terms, reserved;
+    cbx_aggregate_term terms[CBX_AGG_MAX_TERMS];
+} cbx_aggregate;
+typedef struct {
+    int64_t count;
+    uint64_t min_lo, min_hi, max_lo, max_hi;
+    uint64_t sum[3];
+} cbx_aggregate_value;
+typedef struct {
+    int64_t n_rows;
+    cbx_aggregate_value values[CBX_AGG_MAX_TERMS];   /* values[t]: term t; zeros past n_terms */
+} cbx_aggregate_result;
+
+/* Aggregate the records of one source that `filter` keeps (NULL: every record) into *result (host
+ * memory).  Sources (exactly one) as for cbx_filter_records: a selection, framed records, or
+ * fixed-length records; the active segment comes from the selection or from the plan's segment map.
+ * Unlike the filter a plan with Seg_Id levels needs no selection: no seg_state is carried.
+ * n_rec == 0 gives a zeroed result and launches nothing.  Otherwise two launches on `stream`: the
+ * accumulate pass, a grid-stride loop over tiles of 64 records run by at most max_workgroups
+ * workgroups (0: the library's choice; a caller that shares the device gives fewer), each storing one
+ * partial result, and the combine pass, one workgroup that merges them; then one host wait for the
+ * copy of the result.  The result does not depend on max_workgroups.
+ * CBX_E_UNSUPPORTED (reason in cbx_last_error): a field inside an OCCURS; a record-walk plan; UTF-16,
+ * HEX and RAW fields; generated columns; MIN, MAX or SUM on COMP-1 / COMP-2 (a float sum depends on
+ * the order, NaN ordering is not modelled) or on a string field (COUNT is fine for both); and whatever
+ * cbx_filter_records refuses in `filter`.  CBX_E_ARGUMENT: a malformed table, a repeated field, an
+ * empty function mask, max_workgroups < 0. */
+int cbx_aggregate_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                          const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                          int32_t start_offset, const cbx_filter* filter, const cbx_aggregate* aggregate,
+                          int32_t max_workgroups, cbx_aggregate_result* result, void* stream);
+
+/* Durations in ms of the two passes of the plan's last cbx_aggregate_records call, measured with HIP
+ * events on its stream while cbx_plan_set_profiling is on (zeros otherwise). */
+int cbx_aggregate_pass_times(cbx_plan* plan, float* accumulate_ms, float* combine_ms);
 
 /* ---- the record walk with data-dependent offsets ----
  *
