@@ -16,14 +16,14 @@ from __future__ import annotations
 
 import decimal
 from dataclasses import dataclass
-from typing import Any, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import copybook as cbk
 from . import native as N
 from .filter import Unhandled
 
 __all__ = ["AggregateFunc", "CountStar", "Count", "Min", "Max", "Sum", "Slot", "AggregateResult",
-           "compile_aggregates", "Unhandled"]
+           "compile_aggregates", "Unhandled", "KeySlot", "GroupOverflow", "GroupedAggregateResult", "compile_group_by"]
 
 
 class AggregateFunc:
@@ -199,3 +199,139 @@ class AggregateResult:
 
     def __repr__(self) -> str:
         return f"AggregateResult(n_rows={self.n_rows}, values={self.values})"
+
+
+# ---------------------------------------------------------------------------------------------
+# GROUP BY (cbx_aggregate_grouped)
+# ---------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class KeySlot:
+    """One GROUP BY column: its field and the column's type as the plan's field gives it."""
+    field: int
+    is_str: bool
+    out_type: int
+    out_precision: int
+    out_scale: int
+
+
+class GroupOverflow(RuntimeError):
+    """The data holds more distinct keys than max_groups: nothing was returned; call again with a larger max_groups."""
+
+    def __init__(self, max_groups: int):
+        super().__init__(f"more than max_groups = {max_groups} distinct GROUP BY keys; raise max_groups")
+        self.max_groups = max_groups
+
+
+def compile_group_by(plan, columns: Sequence[str]) -> Tuple[N.CbxGroupBy, List[KeySlot]]:
+    """(table, key slots) of GROUP BY `columns` (plain column references); raises Unhandled with the reason when
+    any key cannot be grouped on the GPU -- all or nothing, as compile_aggregates."""
+    columns = list(columns)
+    if not 1 <= len(columns) <= N.CBX_GROUP_MAX_KEYS:
+        raise Unhandled(f"GROUP BY takes 1 to {N.CBX_GROUP_MAX_KEYS} key columns, not {len(columns)}")
+    table = N.CbxGroupBy()
+    keys: List[KeySlot] = []
+    for name in columns:
+        if not isinstance(name, str):
+            raise Unhandled(f"{name!r}: a GROUP BY key must be a plain column reference")
+        try:
+            st = plan.copybook.get_field_by_name(name)
+        except ValueError as e:
+            raise Unhandled(str(e)) from None
+        if not isinstance(st, cbk.Primitive) or id(st) not in plan.field_of_node:
+            raise Unhandled(f"{name}: not a decoded primitive field")
+        fi = plan.field_of_node[id(st)]
+        f = plan.fields[fi]
+        if plan.walk is not None:
+            raise Unhandled(f"{name}: record-walk plan, fields lie at data-dependent offsets")
+        if f.n_dims > 0:
+            raise Unhandled(f"{name}: field inside an OCCURS")
+        if f.kind in (N.K_FLOAT, N.K_DOUBLE):
+            raise Unhandled(f"{name}: COMP-1 / COMP-2 key")
+        is_str = f.kind in _STRING_KINDS
+        if is_str and f.size > N.GROUP_MAX_STRING_KEY_BYTES:
+            raise Unhandled(f"{name}: string key longer than {N.GROUP_MAX_STRING_KEY_BYTES} bytes")
+        if not is_str and f.kind not in _NUMERIC_KINDS:
+            raise Unhandled(f"{name}: UTF-16, HEX and RAW fields are not grouped on the GPU")
+        if any(k.field == fi for k in keys):
+            raise Unhandled(f"{name}: key column repeated")
+        table.fields[table.n_keys] = fi
+        table.n_keys += 1
+        keys.append(KeySlot(fi, is_str, f.out_type, f.out_precision, f.out_scale))
+    return table, keys
+
+
+def check_grouped_functions(slots: Sequence[Slot]) -> None:
+    """MIN / MAX of a DEC128 column is not computed per group (no 128-bit atomic): Unhandled."""
+    for s in slots:
+        if s.out_type == N.O_DEC128 and s.func in (N.AGG_MIN, N.AGG_MAX):
+            raise Unhandled("MIN or MAX of a DEC128 column under GROUP BY")
+
+
+def _key_value(k: KeySlot, cell: N.CbxGroupKey, raw: bytes) -> Any:
+    if cell.is_null:
+        return None
+    if k.is_str:
+        return raw[:cell.str_len].decode("utf-8")
+    v = _signed(cell.hi << 64 | cell.lo, 128)
+    if k.out_type in (N.O_DEC64, N.O_DEC128):
+        with decimal.localcontext() as ctx:
+            ctx.prec = 80
+            return decimal.Decimal(v).scaleb(-k.out_scale)
+    return v
+
+
+def _key_order(key: tuple) -> tuple:
+    return tuple((0, 0) if v is None else (1, v) for v in key)
+
+
+class GroupedAggregateResult:
+    """The result of one pushed grouped aggregation.
+    groups: {key tuple: AggregateResult}, a key value being Spark-typed: int, Decimal at the column's scale, str, or
+            None (all nulls of a key column form one group; "" is a group of its own)."""
+
+    def __init__(self, keys: Sequence[KeySlot], slots: Sequence[Slot], groups: Dict[tuple, AggregateResult]):
+        self.keys = list(keys)
+        self.slots = list(slots)
+        self.groups = groups
+
+    @classmethod
+    def from_arrays(cls, table: N.CbxAggregate, slots: Sequence[Slot], keys: Sequence[KeySlot], strides: N.CbxGroupStrides,
+                    n_groups: int, n_rows, values, cells, key_bytes) -> "GroupedAggregateResult":
+        """From the output arrays of cbx_aggregate_grouped (ctypes arrays sized by max_groups)."""
+        nt, nk = table.n_terms, len(keys)
+        groups: Dict[tuple, AggregateResult] = {}
+        raw = bytes(key_bytes) if key_bytes is not None else b""
+        for g in range(n_groups):
+            key = []
+            for k, ks in enumerate(keys):
+                at = g * strides.str_stride + strides.str_off[k]
+                key.append(_key_value(ks, cells[g * nk + k], raw[at:at + 3 * N.GROUP_MAX_STRING_KEY_BYTES] if ks.is_str else b""))
+            res = N.CbxAggregateResult()
+            res.n_rows = n_rows[g]
+            for t in range(nt):
+                res.values[t] = values[g * nt + t]
+            key = tuple(key)
+            if key in groups:
+                raise AssertionError(f"cbx_aggregate_grouped returned the key {key!r} twice")
+            groups[key] = AggregateResult.from_struct(table, slots, res)
+        return cls(keys, slots, groups)
+
+    @property
+    def n_rows(self) -> int:
+        return sum(r.n_rows for r in self.groups.values())
+
+    def merge(self, other: "GroupedAggregateResult") -> "GroupedAggregateResult":
+        """The result over both sides' (disjoint) records: the union of the keys, AggregateResult.merge where both hold one."""
+        if self.slots != other.slots or self.keys != other.keys:
+            raise ValueError("merge: the two results answer different grouped requests")
+        groups = dict(self.groups)
+        for key, r in other.groups.items():
+            groups[key] = groups[key].merge(r) if key in groups else r
+        return GroupedAggregateResult(self.keys, self.slots, groups)
+
+    def rows(self) -> List[tuple]:
+        """(key values..., aggregate values...) per group, sorted by key, nulls first."""
+        return [tuple(key) + tuple(self.groups[key].values) for key in sorted(self.groups, key=_key_order)]
+
+    def __repr__(self) -> str:
+        return f"GroupedAggregateResult({len(self.groups)} groups, n_rows={self.n_rows})"

@@ -28,6 +28,7 @@
 #include "cbx_chain.h"
 #include "cbx_filter.h"
 #include "cbx_aggregate.h"
+#include "cbx_group.h"
 #include "cbx_gather.h"
 
 using namespace cbx;
@@ -171,6 +172,7 @@ struct cbx_plan {
     struct CallEvents { hipEvent_t e[3]; };
     std::vector<CallEvents> ev_calls;    // recorded, not yet read
     float flt_ms[3] = {0.f, 0.f, 0.f};   // test / scan / emit of the last cbx_filter_records call (profiling)
+    float grp_ms[3] = {0.f, 0.f, 0.f};   // init / accumulate / emit of the last cbx_aggregate_grouped call (profiling)
     float agg_ms[2] = {0.f, 0.f};        // accumulate / combine of the last cbx_aggregate_records call (profiling)
     // the direct projected decode (cbx_gather.h; cbx_plan_options.direct_decode)
     bool direct_ok = false;              // the plan's shape is one the direct kernel decodes
@@ -2483,6 +2485,150 @@ extern "C" int cbx_aggregate_pass_times(cbx_plan* P, float* accumulate_ms, float
     if (!P) return fail(CBX_E_ARGUMENT, "null plan");
     if (accumulate_ms) *accumulate_ms = P->agg_ms[0];
     if (combine_ms) *combine_ms = P->agg_ms[1];
+    return CBX_OK;
+}
+
+// Grouped aggregates (cbx_group.h): table init -> accumulate (find or claim, cached flushes) -> emit.
+namespace {
+struct GroupProgs { AggProg agg; GrpProg grp; FilterProg flt; };
+int group_programs(cbx_plan* P, const cbx_filter* filter, const cbx_aggregate* aggregate, const cbx_group_by* group_by,
+                   int64_t max_groups, GroupProgs* progs, cbx_group_strides* strides, std::string& err) {
+    const int32_t nf = (int32_t)P->hfields.size();
+    int rb = aggregate_build(P->hfields.data(), nf, P->walk, aggregate, &progs->agg, err);
+    if (rb != CBX_OK) return rb;
+    rb = group_build(P->hfields.data(), nf, P->walk, group_by, progs->agg, &progs->grp, err);
+    if (rb != CBX_OK) return rb;
+    if (filter) {
+        rb = filter_build(P->hfields.data(), nf, P->walk, filter, &progs->flt, err);
+        if (rb != CBX_OK) return rb;
+    }
+    return group_strides(P->hfields.data(), group_by, progs->agg.n_terms, max_groups, strides, err);
+}
+}  // namespace
+
+extern "C" int cbx_group_layout(cbx_plan* P, const cbx_group_by* group_by, const cbx_aggregate* aggregate,
+                                int64_t max_groups, cbx_group_strides* strides) {
+    if (!P || !group_by || !aggregate || !strides) return fail(CBX_E_ARGUMENT, "cbx_group_layout: invalid arguments");
+    std::vector<GroupProgs> progs(1);
+    std::string err;
+    const int rb = group_programs(P, nullptr, aggregate, group_by, max_groups, progs.data(), strides, err);
+    return rb == CBX_OK ? CBX_OK : fail(rb, err);
+}
+
+extern "C" int cbx_aggregate_grouped(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                     const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                     int32_t start_offset, const cbx_filter* filter, const cbx_aggregate* aggregate,
+                                     const cbx_group_by* group_by, int64_t max_groups, int32_t max_workgroups,
+                                     const cbx_group_output* out, cbx_group_header* header, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !aggregate || !group_by || !out || !header || n_rec < 0 || n_bytes < 0 || start_offset < 0 || max_workgroups < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_grouped: invalid arguments");
+    memset(header, 0, sizeof(*header));
+    P->grp_ms[0] = P->grp_ms[1] = P->grp_ms[2] = 0.f;
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_grouped: exactly one source (selection, framed records, record stride)");
+    std::vector<GroupProgs> progs(1);
+    std::string err;
+    cbx_group_strides S;
+    const int rb = group_programs(P, filter, aggregate, group_by, max_groups, progs.data(), &S, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    const int nt = progs[0].agg.n_terms, nk = progs[0].grp.n_keys;
+    if (!out->n_rows || !out->keys || (nt > 0 && !out->values) || (S.str_stride > 0 && !out->key_bytes))
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_grouped: output arrays required");
+    if (n_rec == 0) return CBX_OK;
+    if (!d_data || (in && (!in->rec_off || !in->rec_len || !in->segment)))
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_grouped: data and selection arrays required");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_aggregate_grouped: n_rec records of rec_stride bytes exceed n_bytes");
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    int64_t grid = std::min<int64_t>((n_tiles + kAggWaves - 1) / kAggWaves, (int64_t)P->num_cus * 8);
+    if (max_workgroups > 0) grid = std::min<int64_t>(grid, max_workgroups);
+    // block: programs | header words | slot words | slot rows | slot accumulators | out rows | values | keys | key bytes
+    const size_t cap = (size_t)S.capacity, mg = (size_t)max_groups;
+    const size_t o_hdr = (sizeof(GroupProgs) + 63) & ~(size_t)63;
+    const size_t o_slots = o_hdr + 64;
+    const size_t o_rows = o_slots + 8 * cap;
+    const size_t o_acc = o_rows + 8 * cap;
+    const size_t o_orows = o_acc + sizeof(GrpAcc) * cap * (size_t)nt;
+    const size_t o_ovals = o_orows + 8 * mg;
+    const size_t o_okeys = o_ovals + sizeof(cbx_aggregate_value) * mg * (size_t)nt;
+    const size_t o_obytes = o_okeys + sizeof(cbx_group_key) * mg * (size_t)nk;
+    const size_t total = o_obytes + (size_t)S.str_stride * mg + 64;
+    AsyncBlock blk(st);
+    HIP_CHECK(hipMallocAsync(&blk.p, total, st));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    HIP_CHECK(hipMemcpyAsync(b8, progs.data(), filter ? sizeof(GroupProgs) : offsetof(GroupProgs, flt), hipMemcpyHostToDevice, st));
+    GrpArgs g{};
+    FilterArgs& a = g.a.src;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = filter ? (const CBX_CONST FilterProg*)(b8 + offsetof(GroupProgs, flt)) : nullptr;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    g.a.agg = (const CBX_CONST AggProg*)(b8 + offsetof(GroupProgs, agg));
+    g.a.has_filter = filter ? 1 : 0;
+    g.grp = (const CBX_CONST GrpProg*)(b8 + offsetof(GroupProgs, grp));
+    g.t.slots = (uint64_t*)(b8 + o_slots);
+    g.t.rows = (uint64_t*)(b8 + o_rows);
+    g.t.acc = (GrpAcc*)(b8 + o_acc);
+    g.t.hdr = (uint64_t*)(b8 + o_hdr);
+    g.t.capacity = (uint64_t)cap;
+    g.t.max_groups = max_groups;
+    GrpOut o{};
+    o.n_rows = (int64_t*)(b8 + o_orows);
+    o.values = (cbx_aggregate_value*)(b8 + o_ovals);
+    o.keys = (cbx_group_key*)(b8 + o_okeys);
+    o.key_bytes = b8 + o_obytes;
+    o.str_stride = S.str_stride;
+    for (int k = 0; k < CBX_GROUP_MAX_KEYS; k++) o.str_off[k] = S.str_off[k];
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    hipEvent_t* ev = pe.e;
+    if (P->profiling) {
+        for (int k = 0; k < 4; k++) if (!(ev[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    hipLaunchKernelGGL(group_init_kernel, dim3(blocks_for((int64_t)cap, kGrpInitThreads)), dim3(kGrpInitThreads), 0, st, g.t,
+                       (int32_t)nt);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    hipLaunchKernelGGL(group_accumulate_kernel, dim3((unsigned)grid), dim3(kAggThreads), 0, st, g);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(group_emit_kernel, dim3(blocks_for((int64_t)cap, kAggThreads)), dim3(kAggThreads), 0, st, g, o);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[3], st));
+    HIP_CHECK(hipGetLastError());
+    uint64_t hdr[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(hdr, g.t.hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (P->profiling)
+        for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&P->grp_ms[k], ev[k], ev[k + 1]));
+    if (hdr[1] != 0 || (int64_t)hdr[0] > max_groups) {
+        header->overflow = 1;
+        return CBX_OK;
+    }
+    const size_t ng = (size_t)hdr[2];
+    HIP_CHECK(hipMemcpyAsync(out->n_rows, o.n_rows, 8 * ng, hipMemcpyDeviceToHost, st));
+    if (nt > 0) HIP_CHECK(hipMemcpyAsync(out->values, o.values, sizeof(cbx_aggregate_value) * ng * (size_t)nt, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(out->keys, o.keys, sizeof(cbx_group_key) * ng * (size_t)nk, hipMemcpyDeviceToHost, st));
+    if (S.str_stride > 0) HIP_CHECK(hipMemcpyAsync(out->key_bytes, o.key_bytes, (size_t)S.str_stride * ng, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    header->n_groups = (int64_t)ng;
+    for (size_t k = 0; k < ng; k++) header->n_rows += out->n_rows[k];
+    return CBX_OK;
+}
+
+extern "C" int cbx_group_pass_times(cbx_plan* P, float* init_ms, float* accumulate_ms, float* emit_ms) {
+    if (!P) return fail(CBX_E_ARGUMENT, "null plan");
+    if (init_ms) *init_ms = P->grp_ms[0];
+    if (accumulate_ms) *accumulate_ms = P->grp_ms[1];
+    if (emit_ms) *emit_ms = P->grp_ms[2];
     return CBX_OK;
 }
 

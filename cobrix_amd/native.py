@@ -45,7 +45,10 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_plan_set_record_base", "cbx_frame_length_field", "cbx_plan_set_odo_counts",
                     "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline",
                     "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info",
-                    "cbx_aggregate_records", "cbx_aggregate_pass_times")
+                    "cbx_aggregate_records", "cbx_aggregate_pass_times",
+                    "cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
+# grouped aggregates are an additive extension of ABI 24: the version stays, the symbols are required
+GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
 ABI_VERSION = 24
 
 
@@ -177,6 +180,37 @@ class CbxAggregateResult(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_int64), ("values", CbxAggregateValue * CBX_AGG_MAX_TERMS)]
 
 
+# grouped aggregates (cbx_group_by): key limit, workspace limit
+CBX_GROUP_MAX_KEYS = 4
+CBX_GROUP_MAX_WORKSPACE_BYTES = 1 << 30
+GROUP_MAX_STRING_KEY_BYTES = 32
+
+
+class CbxGroupBy(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_int32), ("fields", ctypes.c_int32 * CBX_GROUP_MAX_KEYS),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+class CbxGroupKey(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64), ("is_null", ctypes.c_int32),
+                ("str_len", ctypes.c_int32)]
+
+
+class CbxGroupStrides(ctypes.Structure):
+    _fields_ = [("str_stride", ctypes.c_int32), ("str_off", ctypes.c_int32 * CBX_GROUP_MAX_KEYS),
+                ("reserved", ctypes.c_int32 * 3), ("capacity", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64)]
+
+
+class CbxGroupOutput(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_void_p), ("values", ctypes.c_void_p), ("keys", ctypes.c_void_p),
+                ("key_bytes", ctypes.c_void_p)]
+
+
+class CbxGroupHeader(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int64), ("n_groups", ctypes.c_int64), ("overflow", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 W_GROUP, W_PRIM = 0, 1
 W_REDEFINED, W_REDEFINES = 0x1, 0x2
 
@@ -302,13 +336,19 @@ def load():
                      ("cbx_plan_direct_eligible", [P, P]),
                      ("cbx_plan_launch_info", [P, P]),
                      ("cbx_aggregate_records", [P, P, i64, P, P, P, i64, i32, i32, P, P, i32, P, P]),
-                     ("cbx_aggregate_pass_times", [P, P, P])):
+                     ("cbx_aggregate_pass_times", [P, P, P]),
+                     ("cbx_group_layout", [P, P, P, i64, P]),
+                     ("cbx_aggregate_grouped", [P, P, i64, P, P, P, i64, i32, i32, P, P, P, i64, i32, P, P, P]),
+                     ("cbx_group_pass_times", [P, P, P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):
         # (a diagnostic variant built from an older revision -- tools/build_variant.py -- is timed on the
         # entry points both revisions share)
         raise NativeLibraryError(f"{LIB_PATH}: ABI {L.cbx_abi_version()} != {ABI_VERSION}; rebuild it")
+    missing = [n for n in GROUP_SYMBOLS if not hasattr(L, n)]
+    if missing and not os.environ.get("CBX_LIB_VARIANT"):
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (grouped aggregates); rebuild it")
     _lib = L
     return L
 

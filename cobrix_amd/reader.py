@@ -21,7 +21,8 @@ import numpy as np
 
 from . import copybook as cbk
 from . import native as N
-from .aggregate import AggregateResult, compile_aggregates
+from .aggregate import (AggregateResult, GroupedAggregateResult, GroupOverflow, check_grouped_functions, compile_aggregates,
+                        compile_group_by)
 from .aggregate import Unhandled as AggregateUnhandled
 from .filter import compile_filters
 from .plan import DecodePlan, NativePlan, NeedsWalk, build_plan
@@ -1014,6 +1015,51 @@ class _BaseReader:
         N.check(N.load().cbx_aggregate_pass_times(self.native.handle, ctypes.byref(a), ctypes.byref(c)))
         return a.value, c.value
 
+    def _aggregate_grouped(self, group_by, aggregates, filters, max_groups: int, d_data, n_bytes: int, n_rec: int, st, *,
+                           sel=None, rec_off=None, rec_len=None, stride: int = 0, max_workgroups: int = 0,
+                           header_only: bool = False) -> GroupedAggregateResult:
+        """cbx_aggregate_grouped over one source through the full plan.  All or nothing, as `_aggregate_records`;
+        raises `cobrix_amd.aggregate.GroupOverflow` when the data holds more than max_groups distinct keys.
+        header_only: return (n_groups, n_rows) without mapping the output arrays to Python values (timing tools)."""
+        gtable, keys = compile_group_by(self.plan, group_by)
+        table, slots = compile_aggregates(self.plan, aggregates)
+        check_grouped_functions(slots)
+        flt = None
+        if filters:
+            flt, unhandled = compile_filters(self.plan, filters)
+            if unhandled:
+                raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        max_groups = int(max_groups)
+        L = N.load()
+        strides = N.CbxGroupStrides()
+        N.check(L.cbx_group_layout(self.native.handle, ctypes.byref(gtable), ctypes.byref(table), max_groups,
+                                   ctypes.byref(strides)))
+        nt, nk = table.n_terms, gtable.n_keys
+        n_rows = (ctypes.c_int64 * max_groups)()
+        values = (N.CbxAggregateValue * (max_groups * nt))() if nt else None
+        cells = (N.CbxGroupKey * (max_groups * nk))()
+        key_bytes = (ctypes.c_uint8 * (max_groups * strides.str_stride))() if strides.str_stride else None
+        out = N.CbxGroupOutput(ctypes.addressof(n_rows), ctypes.addressof(values) if nt else None, ctypes.addressof(cells),
+                               ctypes.addressof(key_bytes) if key_bytes is not None else None)
+        hdr = N.CbxGroupHeader()
+        N.check(L.cbx_aggregate_grouped(
+            self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+            rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+            n_rec, stride, self.params.start_offset, ctypes.byref(flt) if flt is not None else None,
+            ctypes.byref(table), ctypes.byref(gtable), max_groups, max_workgroups, ctypes.byref(out), ctypes.byref(hdr),
+            ctypes.c_void_p(st.cuda_stream)))
+        if hdr.overflow:
+            raise GroupOverflow(max_groups)
+        if header_only:
+            return hdr.n_groups, hdr.n_rows
+        return GroupedAggregateResult.from_arrays(table, slots, keys, strides, hdr.n_groups, n_rows, values, cells, key_bytes)
+
+    def group_pass_times(self) -> Tuple[float, float, float]:
+        """(init, accumulate, emit) ms of the last grouped aggregate call (cbx_plan_set_profiling on; zeros otherwise)."""
+        i, a, e = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
+        N.check(N.load().cbx_group_pass_times(self.native.handle, ctypes.byref(i), ctypes.byref(a), ctypes.byref(e)))
+        return i.value, a.value, e.value
+
     def _decode_selection(self, d_data, n_bytes: int, sel: Dict[str, Any], gen_id: bool, st) -> DecodedBatch:
         """cbx_decode_selected into column buffers sized by the selection's row count."""
         n_rec = sel["n"]
@@ -1189,6 +1235,27 @@ class FixedLenNestedReader(_BaseReader):
         self.check_binary_data_validity(len(data))
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
         return self.aggregate_device(t, len(data), aggregates, filters)
+
+    def aggregate_by_device(self, d_data, n_bytes: int, group_by, aggregates, filters=None, max_groups: int = 65536,
+                            stream=None, max_workgroups: int = 0) -> GroupedAggregateResult:
+        """Grouped aggregate pushdown over a split resident in HBM: `aggregate_device` per distinct value of the
+        `group_by` columns (up to four plain column references), computed from the record bytes by
+        cbx_aggregate_grouped.  Keys group by decoded value; NULL is a key of its own.  Raises
+        `cobrix_amd.aggregate.Unhandled` when a key, a function or a filter cannot be evaluated exactly on the GPU and
+        `cobrix_amd.aggregate.GroupOverflow` when there are more than max_groups distinct keys.  Results of several
+        calls combine with `GroupedAggregateResult.merge`."""
+        torch = _torch()
+        stride = self.get_record_size()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        return self._aggregate_grouped(group_by, aggregates, filters, max_groups, d_data, n_bytes, n_bytes // stride, st,
+                                       stride=stride, max_workgroups=max_workgroups)
+
+    def aggregate_by(self, data: bytes, group_by, aggregates, filters=None, max_groups: int = 65536) -> GroupedAggregateResult:
+        """`aggregate_by_device` over host bytes, with the file-size checks of `decode`."""
+        torch = _torch()
+        self.check_binary_data_validity(len(data))
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        return self.aggregate_by_device(t, len(data), group_by, aggregates, filters, max_groups)
 
     def get_row_iterator(self, data: bytes) -> Iterator[dict]:
         return iter(self.decode(data).to_rows())
@@ -1955,6 +2022,37 @@ class VarLenNestedReader(_BaseReader):
             entries = self.generate_index(t, len(data), off, ln, file_id)
         sel = self.select(t, vb, off, ln, entries, file_id)
         return self.aggregate_device(t, vb, sel, aggregates, filters)
+
+    def aggregate_by_device(self, d_data, n_bytes: int, sel_or_framing, group_by, aggregates, filters=None,
+                            max_groups: int = 65536, stream=None, max_workgroups: int = 0) -> GroupedAggregateResult:
+        """Grouped aggregate pushdown over a selection or over framed records (as `aggregate_device`), per distinct
+        value of the `group_by` columns.  Raises `cobrix_amd.aggregate.Unhandled` when a key, a function or a filter
+        cannot be evaluated exactly on the GPU and `cobrix_amd.aggregate.GroupOverflow` past max_groups distinct
+        keys.  Results of several calls combine with `GroupedAggregateResult.merge`."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "aggregates on a hierarchical read: rows are trees of segments")
+        if isinstance(sel_or_framing, dict):
+            return self._aggregate_grouped(group_by, aggregates, filters, max_groups, d_data, n_bytes, sel_or_framing["n"],
+                                           st, sel=sel_or_framing, max_workgroups=max_workgroups)
+        rec_off, rec_len = sel_or_framing
+        return self._aggregate_grouped(group_by, aggregates, filters, max_groups, d_data, n_bytes, int(rec_off.numel()), st,
+                                       rec_off=rec_off, rec_len=rec_len, max_workgroups=max_workgroups)
+
+    def aggregate_by(self, data: bytes, group_by, aggregates, filters=None, max_groups: int = 65536,
+                     file_id: int = 0) -> GroupedAggregateResult:
+        """Grouped aggregate pushdown over a whole file: the row set of `aggregate` (framing, sparse index, selection
+        with segment_filter and file_end_offset, then the filters)."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "aggregates on a hierarchical read: rows are trees of segments")
+        t = self._device_file(data)
+        off, ln, vb = self.frame_file(t, len(data))
+        entries = None
+        if self.index_generation_needed() and not self.params.is_text:
+            entries = self.generate_index(t, len(data), off, ln, file_id)
+        sel = self.select(t, vb, off, ln, entries, file_id)
+        return self.aggregate_by_device(t, vb, sel, group_by, aggregates, filters, max_groups)
 
     def get_row_iterator(self, data: bytes) -> Iterator[dict]:
         return iter(self.read(data).to_rows())

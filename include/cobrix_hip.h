@@ -579,6 +579,83 @@ int cbx_aggregate_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes
  * events on its stream while cbx_plan_set_profiling is on (zeros otherwise). */
 int cbx_aggregate_pass_times(cbx_plan* plan, float* accumulate_ms, float* combine_ms);
 
+/* ---- grouped aggregates (GROUP BY): an additive extension of ABI 24 ----
+ *
+ * SELECT k1..kK, COUNT(*), f(c).. FROM records WHERE filter GROUP BY k1..kK, what pushAggregation hands a
+ * data source when Aggregation.groupByExpressions is not empty.  No structure and no entry point above
+ * changes, so CBX_ABI_VERSION stays 24; a caller checks for the three entry points below.
+ * A key's value is the column's output value exactly as the filter and the aggregates see it: a numeric
+ * key is the signed 128-bit value at the column's scale, a string key the UTF-8 bytes of the trimmed field
+ * through the plan's code page.  Keys group by that decoded value, never by the record's bytes: the sign
+ * nibbles of a COMP-3 zero, the overpunch spellings of one zoned number, strings that differ in trimmed
+ * padding or in two source bytes with one code-page image are one group.  NULL (a malformed numeric, a
+ * numeric reaching past the record's end, a field of an inactive segment redefine, a string starting past
+ * the record's end) is a key value of its own; the empty string is another.
+ * Keys: up to CBX_GROUP_MAX_KEYS distinct fields, numeric (COMP-3, binary, zoned, ASCII numeric, any output
+ * type) or EBCDIC / ASCII strings of at most 32 bytes; a key may also be aggregated.
+ * Per group: n_rows (COUNT(*)) and per term a cbx_aggregate_value with the meaning it has above.  The
+ * order of the groups is unspecified.  The result does not depend on max_workgroups or on timing.
+ * max_groups >= 1 bounds the number of distinct keys: the call gives the exact result when there are at
+ * most max_groups of them, and otherwise sets header->overflow (status CBX_OK): no group data is to be
+ * trusted then.  The workspace is a table of `capacity` slots (the power of two >= 2 * max_groups) of
+ * 16 + 64 * n_terms bytes plus device copies of the output arrays; CBX_E_ARGUMENT when it would exceed
+ * CBX_GROUP_MAX_WORKSPACE_BYTES. */
+#define CBX_GROUP_MAX_KEYS 4
+#define CBX_GROUP_MAX_WORKSPACE_BYTES 0x40000000ll   /* 1 GiB */
+typedef struct {
+    int32_t n_keys;                        /* 1 .. CBX_GROUP_MAX_KEYS */
+    int32_t fields[CBX_GROUP_MAX_KEYS];    /* indices into the plan's cbx_field table, no repeats */
+    int32_t reserved[3];
+} cbx_group_by;
+typedef struct {
+    uint64_t lo, hi;       /* numeric key: 128-bit two's complement at the column's scale; zero otherwise */
+    int32_t is_null;
+    int32_t str_len;       /* string key: UTF-8 bytes at key_bytes[g * str_stride + str_off[k]]; else 0 */
+} cbx_group_key;
+typedef struct {
+    int32_t str_stride;                    /* bytes of key_bytes per group (3 per source byte of every string key) */
+    int32_t str_off[CBX_GROUP_MAX_KEYS];   /* where key k's bytes start inside a group's stride */
+    int32_t reserved[3];
+    int64_t capacity;                      /* slots of the table */
+    int64_t workspace_bytes;               /* device memory the call allocates from the stream's pool */
+} cbx_group_strides;
+typedef struct {
+    int64_t* n_rows;                 /* [max_groups] */
+    cbx_aggregate_value* values;     /* [max_groups][n_terms], NULL when n_terms == 0 */
+    cbx_group_key* keys;             /* [max_groups][n_keys] */
+    uint8_t* key_bytes;              /* [max_groups][str_stride], NULL when str_stride == 0 */
+} cbx_group_output;
+typedef struct {
+    int64_t n_rows;        /* records the filter keeps (the sum of the groups' n_rows) */
+    int64_t n_groups;
+    int32_t overflow;      /* more than max_groups distinct keys: nothing else is to be trusted */
+    int32_t reserved;
+} cbx_group_header;
+
+/* The strides and the workspace size of a grouped call: validates the tables as the call itself does. */
+int cbx_group_layout(cbx_plan* plan, const cbx_group_by* group_by, const cbx_aggregate* aggregate,
+                     int64_t max_groups, cbx_group_strides* strides);
+
+/* As cbx_aggregate_records, per distinct key of `group_by`: out's host arrays (sized by max_groups and the
+ * strides above) receive header->n_groups groups.  n_rec == 0 launches nothing and gives zero groups.
+ * Otherwise, on `stream`: the table's init, the accumulate pass (one lane per record finds or claims its
+ * key's slot -- a slot names a representative record, its key is that record's key -- and the tile's values
+ * go through a wave-private cache of running accumulators to device-scope 64-bit atomics), the emit pass
+ * (one lane per slot); then a host wait for the header and one for the copies of exactly n_groups groups.
+ * CBX_E_UNSUPPORTED (reason in cbx_last_error): whatever cbx_aggregate_records refuses for a field or in
+ * `filter`; a COMP-1 / COMP-2 key; a string key longer than 32 bytes; MIN or MAX of a DEC128 column (there
+ * is no 128-bit atomic; COUNT and SUM of it are fine).  CBX_E_ARGUMENT: a malformed table, a repeated key,
+ * max_groups < 1, a workspace above the limit. */
+int cbx_aggregate_grouped(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                          const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                          int32_t start_offset, const cbx_filter* filter, const cbx_aggregate* aggregate,
+                          const cbx_group_by* group_by, int64_t max_groups, int32_t max_workgroups,
+                          const cbx_group_output* out, cbx_group_header* header, void* stream);
+
+/* Durations in ms of the passes of the plan's last cbx_aggregate_grouped call (init, accumulate, emit),
+ * measured with HIP events on its stream while cbx_plan_set_profiling is on (zeros otherwise). */
+int cbx_group_pass_times(cbx_plan* plan, float* init_ms, float* accumulate_ms, float* emit_ms);
+
 /* ---- the record walk with data-dependent offsets ----
  *
  * Layouts the static-offset tables above cannot express run through a per-record walk of the
