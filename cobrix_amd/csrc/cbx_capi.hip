@@ -131,6 +131,7 @@ struct cbx_plan {
     std::string jit_error;
     int last_kind = 0;
     cbx_launch_info last_info{};   // cbx_plan_launch_info: how launch() ran the last decode call
+    cbx_walk_info last_walk{};     // cbx_plan_walk_info: how walk_launch() ran the last decode call (kind 0: it did not)
     int32_t* d_status = nullptr;
     int num_cus = 256;
     // record walk (cbx_plan_set_walk, cbx_walk.h)
@@ -1462,6 +1463,11 @@ static int walk_launch(cbx_plan* P, const CallShape& c, cbx_column* columns, hip
     }
     P->last_kind = jfn ? 3 : 2;
     P->last_info = cbx_launch_info{};
+    cbx_walk_info wi{};
+    wi.kind = P->last_kind; wi.stage_cap = a.stage_cap; wi.vlds = a.vlds; wi.wave_lds = a.wave_lds;
+    wi.depth = a.depth; wi.stack_lds = a.stack_lds; wi.n_vslots = a.n_vslots; wi.n_sslots = a.n_sslots;
+    wi.grid = grid; wi.n_tiles = n_tiles;
+    P->last_walk = wi;
     return CBX_OK;
 }
 
@@ -1691,6 +1697,14 @@ extern "C" int cbx_plan_launch_info(cbx_plan* P, cbx_launch_info* out) {
     if (!P || !out) return fail(CBX_E_ARGUMENT, "cbx_plan_launch_info: invalid arguments");
     *out = P->last_info;
     out->kind = P->last_kind;
+    return CBX_OK;
+}
+
+extern "C" int cbx_plan_walk_info(cbx_plan* P, cbx_walk_info* out) {
+    if (!P || !out) return fail(CBX_E_ARGUMENT, "cbx_plan_walk_info: invalid arguments");
+    if (P->last_kind != 2 && P->last_kind != 3)
+        return fail(CBX_E_STATE, "cbx_plan_walk_info: the plan's last decode call was not a record walk");
+    *out = P->last_walk;
     return CBX_OK;
 }
 

@@ -44,12 +44,12 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_hier_list_offsets", "cbx_plan_set_walk", "cbx_frame_var_occurs",
                     "cbx_plan_set_record_base", "cbx_frame_length_field", "cbx_plan_set_odo_counts",
                     "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline",
-                    "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info",
+                    "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info", "cbx_plan_walk_info",
                     "cbx_aggregate_records", "cbx_aggregate_pass_times",
                     "cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
-# grouped aggregates are an additive extension of ABI 24: the version stays, the symbols are required
+# grouped aggregates were an additive extension of ABI 24: the symbols are required
 GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class NativeLibraryError(RuntimeError):
@@ -276,6 +276,19 @@ def launch_info(plan_handle) -> CbxLaunchInfo:
     return info
 
 
+class CbxWalkInfo(ctypes.Structure):
+    """cbx_plan_walk_info: how the plan's last decode call launched the record walk."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "stage_cap", "vlds", "wave_lds", "depth", "stack_lds",
+                                                "n_vslots", "n_sslots")] + \
+               [("grid", ctypes.c_int64), ("n_tiles", ctypes.c_int64)]
+
+
+def walk_info(plan_handle) -> CbxWalkInfo:
+    info = CbxWalkInfo()
+    check(load().cbx_plan_walk_info(plan_handle, ctypes.byref(info)))
+    return info
+
+
 _lib = None
 
 
@@ -335,6 +348,7 @@ def load():
                      ("cbx_filter_pass_times", [P, P, P, P]),
                      ("cbx_plan_direct_eligible", [P, P]),
                      ("cbx_plan_launch_info", [P, P]),
+                     ("cbx_plan_walk_info", [P, P]),
                      ("cbx_aggregate_records", [P, P, i64, P, P, P, i64, i32, i32, P, P, i32, P, P]),
                      ("cbx_aggregate_pass_times", [P, P, P]),
                      ("cbx_group_layout", [P, P, P, i64, P]),

@@ -43,7 +43,7 @@ typedef __hip_internal::uint64_t uint64_t;
 extern "C" {
 #endif
 
-#define CBX_ABI_VERSION 24
+#define CBX_ABI_VERSION 25
 
 /* status codes */
 #define CBX_OK 0
@@ -329,6 +329,23 @@ typedef struct cbx_launch_info {
     int64_t grid, blocks_needed;   /* workgroups launched / workgroups that cover every tile once */
 } cbx_launch_info;
 int cbx_plan_launch_info(cbx_plan* plan, cbx_launch_info* out);
+
+/* How the plan's last decode call launched the record walk (cbx_plan_set_walk; read-only, tests pin the
+ * dispatch with it).  CBX_E_STATE when the plan's last decode call was not a walk (kind 2 / 3).  Whether
+ * a given tile was staged depends on the data: a tile whose records span lo..hi bytes of the data is
+ * staged when hi - lo + ((data + lo) & 15) <= stage_cap, and read from HBM otherwise. */
+typedef struct cbx_walk_info {
+    int32_t kind;          /* 2 the table-driven walk, 3 its copybook-specialised form */
+    int32_t stage_cap;     /* LDS bytes per wave for a tile's record span (0: CBX_WALK_NO_STAGE) */
+    int32_t vlds;          /* validity words and string cursors accumulate in LDS (0: global atomics) */
+    int32_t wave_lds;      /* LDS bytes per wave: frame stack + stage + (vlds) words and cursors */
+    int32_t depth;         /* frame-stack depth of the copybook */
+    int32_t stack_lds;     /* LDS bytes of the frame stack per wave (0 for kind 3: frames in registers) */
+    int32_t n_vslots;      /* validity words per tile: every slot of every column */
+    int32_t n_sslots;      /* string column slots (one payload cursor each) */
+    int64_t grid, n_tiles; /* workgroups launched (4 waves each) / tiles of 64 records */
+} cbx_walk_info;
+int cbx_plan_walk_info(cbx_plan* plan, cbx_walk_info* out);
 
 /* Whether decode calls of the plan would run the direct kernel with direct_decode = 1: *eligible = 1,
  * or 0 with the reason in cbx_last_error().  Eligible: no record walk, no OCCURS array, no list

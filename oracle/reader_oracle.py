@@ -396,9 +396,14 @@ class VarRecord:
 
 
 def var_len_records(cb: cbk.Copybook, data: bytes, p, file_id: int = 0,
-                    entries: Optional[List[Entry]] = None) -> List[VarRecord]:
-    """The records VarLenNestedIterator returns for every index entry, in file order."""
+                    entries: Optional[List[Entry]] = None, payloads: Optional[List[bytes]] = None) -> List[VarRecord]:
+    """The records VarLenNestedIterator returns for every index entry, in file order.  payloads: the
+    records a raw record extractor returned (VRLRecordReader.fetchNext, :80-86) instead of RDW / length
+    field framing, as one entry; their segment id, Seg_Id levels and filter are those of any record
+    (VRLRecordReader.scala:100-104, VarLenNestedIterator.scala:88-93)."""
     rp = header_parser(cb, p)
+    if payloads is not None:
+        entries = [Entry(0, -1, file_id, 0)]
     if entries is None:
         entries = sparse_index(cb, data, p, file_id) if index_generation_needed(p) else [Entry(0, -1, file_id, 0)]
     seg_reader = FieldReader(cb, cb.get_field_by_name(p.segment_field)) if p.segment_field else None
@@ -412,8 +417,13 @@ def var_len_records(cb: cbk.Copybook, data: bytes, p, file_id: int = 0,
         acc = SegmentIdAccumulator(levels, p.segment_id_prefix, e.file_id) if p.segment_field else None
         record_index = e.record_index - 1
         lf = LengthFieldReader(cb, p) if (getattr(p, "record_length_field", None) and not p.is_record_sequence) else None
+        extracted = iter(payloads) if payloads is not None else None
         while True:
-            if lf is not None:
+            if extracted is not None:
+                rec = next(extracted, None)
+                if rec is None:
+                    break
+            elif lf is not None:
                 rec = lf.fetch(s)
                 if rec is None:
                     break
@@ -614,8 +624,7 @@ def var_len_rows(cb: cbk.Copybook, data: bytes, p, file_id: int = 0,
         return hier_rows(cb, data, p, file_id, entries)
     if p.variable_size_occurs and not p.is_record_sequence and not p.is_text:
         # VarOccursRecordExtractor framing (VarLenNestedReader.recordExtractor, :60-78); one index entry
-        payloads = var_occurs_records(cb, data)
-        recs = [VarRecord(b, i, [], None) for i, b in enumerate(payloads)]
+        recs = var_len_records(cb, data, p, file_id, payloads=var_occurs_records(cb, data))
     else:
         recs = var_len_records(cb, data, p, file_id, entries)
     res = O.decode_records(cb, [r.payload for r in recs], start_offset=p.start_offset,

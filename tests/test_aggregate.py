@@ -266,7 +266,7 @@ def test_aggregate_struct_layout_matches_header(tmp_path):
         got = ctypes.sizeof(py) if what == "sizeof" else getattr(py, what).offset
         assert got == int(val), f"{cname}.{what}: ctypes {got} != C {val}"
     assert seen == len(consts) + sum(1 + len(py._fields_) for py in AGG_STRUCTS.values())
-    assert N.ABI_VERSION == 24 and {"cbx_aggregate_records", "cbx_aggregate_pass_times"} <= set(N.EXPORTED_SYMBOLS)
+    assert N.ABI_VERSION == 25 and {"cbx_aggregate_records", "cbx_aggregate_pass_times"} <= set(N.EXPORTED_SYMBOLS)
 
 
 # ---------------------------------------------------------------------------------------------

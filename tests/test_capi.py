@@ -32,7 +32,7 @@ STRUCTS = {"cbx_field": N.CbxField, "cbx_array": N.CbxArray, "cbx_segment_map": 
            "cbx_hier_params": N.CbxHierParams, "cbx_walk_node": N.CbxWalkNode, "cbx_walk_array": N.CbxWalkArray,
            "cbx_walk_handler": N.CbxWalkHandler, "cbx_hier_dependee": N.CbxHierDependee,
            "cbx_hier_odo_array": N.CbxHierOdoArray, "cbx_hier_walk": N.CbxHierWalk,
-           "cbx_launch_info": N.CbxLaunchInfo}
+           "cbx_launch_info": N.CbxLaunchInfo, "cbx_walk_info": N.CbxWalkInfo}
 
 
 def test_struct_layout_matches_header(tmp_path):

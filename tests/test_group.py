@@ -166,7 +166,7 @@ def test_group_struct_layout_matches_header(tmp_path):
             got = ctypes.sizeof(py) if what == "sizeof" else getattr(py, what).offset
             assert got == int(val), f"{cname}.{what}: ctypes {got} != C {val}"
     assert seen == len(consts) + 1 + sum(1 + len(py._fields_) for py in GROUP_STRUCTS.values())
-    assert N.ABI_VERSION == 24 and set(N.GROUP_SYMBOLS) <= set(N.EXPORTED_SYMBOLS)
+    assert N.ABI_VERSION == 25 and set(N.GROUP_SYMBOLS) <= set(N.EXPORTED_SYMBOLS)
     assert set(N.GROUP_SYMBOLS) == {"cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times"}
 
 
