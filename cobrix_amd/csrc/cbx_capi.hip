@@ -29,6 +29,7 @@
 #include "cbx_filter.h"
 #include "cbx_aggregate.h"
 #include "cbx_group.h"
+#include "cbx_topn.h"
 #include "cbx_gather.h"
 
 using namespace cbx;
@@ -175,6 +176,8 @@ struct cbx_plan {
     float flt_ms[3] = {0.f, 0.f, 0.f};   // test / scan / emit of the last cbx_filter_records call (profiling)
     float grp_ms[3] = {0.f, 0.f, 0.f};   // init / accumulate / emit of the last cbx_aggregate_grouped call (profiling)
     float agg_ms[2] = {0.f, 0.f};        // accumulate / combine of the last cbx_aggregate_records call (profiling)
+    float topn_ms[3] = {0.f, 0.f, 0.f};  // key / select / emit of the last cbx_top_n_records call (profiling)
+    cbx_topn_info last_topn{};           // cbx_top_n_info: how the last cbx_top_n_records call ran
     // the direct projected decode (cbx_gather.h; cbx_plan_options.direct_decode)
     bool direct_ok = false;              // the plan's shape is one the direct kernel decodes
     std::string direct_why;              // why not
@@ -2643,6 +2646,195 @@ extern "C" int cbx_group_pass_times(cbx_plan* P, float* init_ms, float* accumula
     if (init_ms) *init_ms = P->grp_ms[0];
     if (accumulate_ms) *accumulate_ms = P->grp_ms[1];
     if (emit_ms) *emit_ms = P->grp_ms[2];
+    return CBX_OK;
+}
+
+// Top-N / LIMIT (cbx_topn.h): key pass -> per level (8 x (histogram, pick), classify, one host wait, tie list)
+// -> count, scan, emit.
+extern "C" int cbx_top_n_records(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                 const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                 int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                                 const cbx_sort_order* order, int64_t limit, int32_t max_workgroups, cbx_selection* out,
+                                 int64_t* n_selected, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !order || !out || !n_selected || n_rec < 0 || n_bytes < 0 || start_offset < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_top_n_records: invalid arguments");
+    *n_selected = 0;
+    P->topn_ms[0] = P->topn_ms[1] = P->topn_ms[2] = 0.f;
+    P->last_topn = cbx_topn_info{};
+    if (limit < 0) return fail(CBX_E_ARGUMENT, "cbx_top_n_records: limit < 0");
+    if (max_workgroups < 0) return fail(CBX_E_ARGUMENT, "cbx_top_n_records: max_workgroups < 0");
+    if (n_rec > 0x7fffffffll) return fail(CBX_E_ARGUMENT, "cbx_top_n_records: n_rec > INT32_MAX (split the batch)");
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_top_n_records: exactly one source (selection, framed records, record stride)");
+    const int L = P->opts.has_segments ? P->opts.segments.n_levels : 0;
+    if (!in && L > 0)
+        return fail(CBX_E_ARGUMENT, "cbx_top_n_records: a plan with Seg_Id levels takes a selection (cbx_select_records)");
+    struct Progs { TopnProg topn; FilterProg flt; };
+    std::vector<Progs> progs(1);
+    std::string err;
+    int rb = topn_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, order, &progs[0].topn, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    if (filter) {
+        rb = filter_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, filter, &progs[0].flt, err);
+        if (rb != CBX_OK) return fail(rb, err);
+    }
+    cbx_topn_info& info = P->last_topn;
+    info.levels_total = progs[0].topn.n_words + 1;
+    for (int k = 0; k < progs[0].topn.n_keys; k++) info.words_per_key[k] = topn_words_of_key(progs[0].topn, k);
+    if (in) out->file_id = in->file_id;
+    if (n_rec == 0) return CBX_OK;
+    if (limit == 0) { info.n_live = -1; return CBX_OK; }
+    if (!d_data || !out->rec_off || !out->rec_len || !out->record_id || !out->segment ||
+        (in && (!in->rec_off || !in->rec_len || !in->record_id || !in->segment)) ||
+        (in && L > 0 && (!in->seg_state || !out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_top_n_records: selection arrays required");
+    if (in && (in->rec_off == out->rec_off || in->rec_len == out->rec_len || in->record_id == out->record_id ||
+               in->segment == out->segment || (L > 0 && in->seg_state == out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_top_n_records: out must not share arrays with in");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_top_n_records: n_rec records of rec_stride bytes exceed n_bytes");
+    const bool select = limit < n_rec;   // (limit >= n_rec: the live records are the result)
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    const int64_t nb = scan_sums_len(n_tiles + 1);
+    // block: programs | state | bins (8 x 256) | live (n_tiles) | keep (n_tiles) | base (n_tiles + 1) | sums (nb) |
+    //        counts (n_tiles + 1) | words (n_rec) | segments (n_rec)
+    const size_t o_state = (sizeof(Progs) + 63) & ~(size_t)63;
+    const size_t o_bins = o_state + sizeof(uint64_t) * TS_WORDS;
+    const size_t o_live = o_bins + sizeof(uint32_t) * 8 * 256;
+    const size_t o_keep = o_live + sizeof(uint64_t) * n_tiles;
+    const size_t o_base = o_keep + sizeof(uint64_t) * n_tiles;
+    const size_t o_sums = o_base + sizeof(int64_t) * (n_tiles + 1);
+    const size_t o_cnt = o_sums + sizeof(int64_t) * nb;
+    const size_t o_words = (o_cnt + sizeof(uint32_t) * (n_tiles + 2) + 7) & ~(size_t)7;
+    const size_t o_seg = o_words + (select ? sizeof(uint64_t) * (size_t)n_rec : 0);
+    const bool map_seg = !in && P->opts.has_segments;
+    AsyncBlock blk(st), lists(st);
+    HIP_CHECK(hipMallocAsync(&blk.p, o_seg + (map_seg ? sizeof(int16_t) * (size_t)n_rec : 0) + 16, st));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    int64_t* base = (int64_t*)(b8 + o_base);
+    int64_t* sums = (int64_t*)(b8 + o_sums);
+    uint32_t* counts = (uint32_t*)(b8 + o_cnt);
+    uint64_t* state = (uint64_t*)(b8 + o_state);
+    HIP_CHECK(hipMemcpyAsync(b8, progs.data(), filter ? sizeof(Progs) : sizeof(TopnProg), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(counts + n_tiles, 0, sizeof(uint32_t), st));
+    TopnArgs g{};
+    FilterArgs& a = g.src;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = filter ? (const CBX_CONST FilterProg*)(b8 + offsetof(Progs, flt)) : nullptr;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    a.keep = (uint64_t*)(b8 + o_keep);
+    a.counts = counts;
+    a.seg_out = map_seg ? (int16_t*)(b8 + o_seg) : nullptr;
+    g.topn = (const CBX_CONST TopnProg*)b8;
+    g.has_filter = filter ? 1 : 0;
+    g.want_words = select ? 1 : 0;
+    g.live = (uint64_t*)(b8 + o_live);
+    g.words = select ? (uint64_t*)(b8 + o_words) : nullptr;
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    hipEvent_t* ev = pe.e;
+    if (P->profiling) {
+        for (int k = 0; k < 4; k++) if (!(ev[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    const unsigned tile_grid = blocks_for(n_tiles, kFltThreads / kWave);
+    hipLaunchKernelGGL(topn_key_kernel, dim3(tile_grid), dim3(kFltThreads), 0, st, g);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    HIP_CHECK(hipGetLastError());
+    info.n_live = -1;
+    if (select) {
+        uint64_t h_state[TS_WORDS] = {};
+        h_state[TS_NEED] = (uint64_t)limit;
+        HIP_CHECK(hipMemcpyAsync(state, h_state, sizeof(h_state), hipMemcpyHostToDevice, st));
+        TopnCand c{};
+        c.words = g.words; c.live = g.live; c.list = nullptr; c.count = n_rec;
+        c.state = state; c.bins = (uint32_t*)(b8 + o_bins);
+        size_t half = 0;   // the two tie buffers (a level reads one and fills the other): sized once, after level 0
+        for (int level = 0;; level++) {
+            int64_t grid = std::min<int64_t>((c.count + kTopnThreads - 1) / kTopnThreads, (int64_t)P->num_cus * 8);
+            if (max_workgroups > 0) grid = std::min<int64_t>(grid, max_workgroups);
+            grid = std::max<int64_t>(grid, 1);
+            if (level == 0) info.grid = grid;
+            HIP_CHECK(hipMemsetAsync(c.bins, 0, sizeof(uint32_t) * 8 * 256, st));
+            for (int round = 0; round < 8; round++) {
+                hipLaunchKernelGGL(topn_hist_kernel, dim3((unsigned)grid), dim3(kTopnThreads), 0, st, c, (int32_t)round);
+                hipLaunchKernelGGL(topn_pick_kernel, dim3(1), dim3(64), 0, st, c, (int32_t)round, (int32_t)level);
+            }
+            if (level == 0)
+                hipLaunchKernelGGL(topn_classify_tiles_kernel, dim3((unsigned)grid), dim3(kTopnThreads), 0, st, c, n_tiles, a.keep);
+            else
+                hipLaunchKernelGGL(topn_classify_list_kernel, dim3((unsigned)grid), dim3(kTopnThreads), 0, st, c, a.keep);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(h_state, state, sizeof(h_state), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));   // the level's one wait
+            info.levels_run = level + 1;
+            if (level == 0) info.n_live = (int64_t)h_state[TS_TOTAL];
+            if (h_state[TS_ALL] || h_state[TS_TIES] == h_state[TS_NEED]) break;   // classify kept the whole class
+            if (level + 1 >= info.levels_total)
+                return fail(CBX_E_STATE, "cbx_top_n_records: the source index did not decide (internal error)");
+            const int64_t ties = (int64_t)h_state[TS_TIES];
+            if (level == 0) info.ties_after_level0 = ties;
+            info.ties_max = std::max(info.ties_max, ties);
+            // the next level's candidates: words (8 bytes) in front of indices (4 bytes).  A class only shrinks,
+            // so both buffers take the size of level 0's class -- one allocation per call, not one per level
+            if (level == 0) {
+                half = ((size_t)ties * 12 + 63) & ~(size_t)63;
+                HIP_CHECK(hipMallocAsync(&lists.p, 2 * half, st));
+            }
+            uint8_t* nbuf = (uint8_t*)lists.p + ((level & 1) ? half : 0);
+            uint64_t* n_words = (uint64_t*)nbuf;
+            int32_t* n_list = (int32_t*)(nbuf + (size_t)ties * 8);
+            hipLaunchKernelGGL(topn_tie_kernel, dim3((unsigned)grid), dim3(kTopnThreads), 0, st, g, c, (int32_t)(level + 1), ties,
+                               n_list, n_words);
+            HIP_CHECK(hipGetLastError());
+            // the next level: prefix, ties and the list cursor start over; `need` goes on
+            HIP_CHECK(hipMemsetAsync(state + TS_PREFIX, 0, sizeof(uint64_t), st));
+            HIP_CHECK(hipMemsetAsync(state + TS_TIES, 0, sizeof(uint64_t), st));
+            HIP_CHECK(hipMemsetAsync(state + TS_LIST, 0, sizeof(uint64_t), st));
+            c.words = n_words; c.live = nullptr; c.list = n_list; c.count = ties;
+        }
+    }
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(topn_count_kernel, dim3(blocks_for(n_tiles, kTopnThreads)), dim3(kTopnThreads), 0, st,
+                       (const uint64_t*)a.keep, n_tiles, counts);
+    device_scan(counts, n_tiles + 1, base, sums, st);
+    cbx_selection none{};
+    hipLaunchKernelGGL(filter_emit_kernel, dim3(tile_grid), dim3(kFltThreads), 0, st, a, (const int64_t*)base, in ? *in : none,
+                       in ? 1 : 0, L > 0 ? 1 + L : 0, first_record_id, *out);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[3], st));
+    HIP_CHECK(hipGetLastError());
+    int64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, base + n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (P->profiling)
+        for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&P->topn_ms[k], ev[k], ev[k + 1]));
+    if (!select) info.n_live = total;
+    *n_selected = total;
+    return CBX_OK;
+}
+
+extern "C" int cbx_top_n_info(cbx_plan* P, cbx_topn_info* out) {
+    if (!P || !out) return fail(CBX_E_ARGUMENT, "cbx_top_n_info: invalid arguments");
+    *out = P->last_topn;
+    return CBX_OK;
+}
+
+extern "C" int cbx_top_n_pass_times(cbx_plan* P, float* key_ms, float* select_ms, float* emit_ms) {
+    if (!P) return fail(CBX_E_ARGUMENT, "null plan");
+    if (key_ms) *key_ms = P->topn_ms[0];
+    if (select_ms) *select_ms = P->topn_ms[1];
+    if (emit_ms) *emit_ms = P->topn_ms[2];
     return CBX_OK;
 }
 

@@ -46,9 +46,12 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_hier_dependee_counts", "cbx_hier_dependee_values", "cbx_plan_set_dep_seed", "cbx_views_to_utf8", "cbx_plan_pipeline",
                     "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info", "cbx_plan_walk_info",
                     "cbx_aggregate_records", "cbx_aggregate_pass_times",
-                    "cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
+                    "cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times",
+                    "cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times")
 # grouped aggregates were an additive extension of ABI 24: the symbols are required
 GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
+# Top-N / LIMIT pushdown was an additive extension of ABI 25: the symbols are required
+TOPN_SYMBOLS = ("cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times")
 ABI_VERSION = 25
 
 
@@ -211,6 +214,26 @@ class CbxGroupHeader(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+# Top-N (cbx_sort_order): key limit, flag bits
+CBX_TOPN_MAX_KEYS = 4
+SORT_DESC, SORT_NULLS_LAST = 1, 2
+
+
+class CbxSortKey(ctypes.Structure):
+    _fields_ = [("field", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class CbxSortOrder(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_int32), ("reserved", ctypes.c_int32), ("keys", CbxSortKey * CBX_TOPN_MAX_KEYS)]
+
+
+class CbxTopnInfo(ctypes.Structure):
+    """cbx_top_n_info: how the plan's last Top-N call ran."""
+    _fields_ = [("n_live", ctypes.c_int64), ("ties_after_level0", ctypes.c_int64), ("ties_max", ctypes.c_int64),
+                ("grid", ctypes.c_int64), ("levels_run", ctypes.c_int32), ("levels_total", ctypes.c_int32),
+                ("words_per_key", ctypes.c_int32 * CBX_TOPN_MAX_KEYS)]
+
+
 W_GROUP, W_PRIM = 0, 1
 W_REDEFINED, W_REDEFINES = 0x1, 0x2
 
@@ -353,7 +376,10 @@ def load():
                      ("cbx_aggregate_pass_times", [P, P, P]),
                      ("cbx_group_layout", [P, P, P, i64, P]),
                      ("cbx_aggregate_grouped", [P, P, i64, P, P, P, i64, i32, i32, P, P, P, i64, i32, P, P, P]),
-                     ("cbx_group_pass_times", [P, P, P, P])):
+                     ("cbx_group_pass_times", [P, P, P, P]),
+                     ("cbx_top_n_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, i64, i32, P, P, P]),
+                     ("cbx_top_n_info", [P, P]),
+                     ("cbx_top_n_pass_times", [P, P, P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):
@@ -363,6 +389,9 @@ def load():
     missing = [n for n in GROUP_SYMBOLS if not hasattr(L, n)]
     if missing and not os.environ.get("CBX_LIB_VARIANT"):
         raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (grouped aggregates); rebuild it")
+    missing = [n for n in TOPN_SYMBOLS if not hasattr(L, n)]
+    if missing and not os.environ.get("CBX_LIB_VARIANT"):
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (Top-N pushdown); rebuild it")
     _lib = L
     return L
 

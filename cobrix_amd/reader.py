@@ -26,6 +26,7 @@ from .aggregate import (AggregateResult, GroupedAggregateResult, GroupOverflow, 
 from .aggregate import Unhandled as AggregateUnhandled
 from .filter import compile_filters
 from .plan import DecodePlan, NativePlan, NeedsWalk, build_plan
+from .topn import compile_order
 from .schema import ST_DECIMAL, spark_schema
 
 _CTX = Context(prec=200)
@@ -1060,6 +1061,48 @@ class _BaseReader:
         N.check(N.load().cbx_group_pass_times(self.native.handle, ctypes.byref(i), ctypes.byref(a), ctypes.byref(e)))
         return i.value, a.value, e.value
 
+    def _top_n_records(self, orders, limit: int, filters, d_data, n_bytes: int, n_rec: int, st, *, sel=None, rec_off=None,
+                       rec_len=None, stride: int = 0, first_record_id: int = 0, file_id: int = 0,
+                       max_workgroups: int = 0) -> Dict[str, Any]:
+        """cbx_top_n_records over one source (a selection, framed records, fixed-length records) through the
+        full plan: of the rows `filters` keep, the min(limit, kept) that come first under `orders`, in source
+        order, as a selection for cbx_decode_selected.  All or nothing: raises `cobrix_amd.topn.Unhandled` when
+        a key cannot be ordered on the GPU, or when a filter cannot be compiled (a Top-N over unfiltered rows
+        would be wrong)."""
+        table = compile_order(self.plan, orders)
+        flt = None
+        if filters:
+            flt, unhandled = compile_filters(self.plan, filters)
+            if unhandled:
+                raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        limit = int(limit)
+        out, cs = self._empty_selection(min(n_rec, max(limit, 0)), d_data.device)
+        cs.file_id = sel["struct"].file_id if sel is not None else file_id
+        ns = ctypes.c_int64(0)
+        N.check(N.load().cbx_top_n_records(
+            self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+            rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+            n_rec, stride, self.params.start_offset, first_record_id, ctypes.byref(flt) if flt is not None else None,
+            ctypes.byref(table), limit, max_workgroups, ctypes.byref(cs), ctypes.byref(ns),
+            ctypes.c_void_p(st.cuda_stream)))
+        out["n"] = ns.value
+        out["struct"] = cs
+        out["source"] = sel   # (the input selection's arrays stay alive with the result)
+        out["unhandled"] = []
+        return out
+
+    def topn_info(self) -> N.CbxTopnInfo:
+        """How the last Top-N call ran (cbx_top_n_info): live rows, select levels, tie classes, grid."""
+        info = N.CbxTopnInfo()
+        N.check(N.load().cbx_top_n_info(self.native.handle, ctypes.byref(info)))
+        return info
+
+    def topn_pass_times(self) -> Tuple[float, float, float]:
+        """(key, select, emit) ms of the last Top-N call (cbx_plan_set_profiling on; zeros otherwise)."""
+        k, s_, e = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
+        N.check(N.load().cbx_top_n_pass_times(self.native.handle, ctypes.byref(k), ctypes.byref(s_), ctypes.byref(e)))
+        return k.value, s_.value, e.value
+
     def _decode_selection(self, d_data, n_bytes: int, sel: Dict[str, Any], gen_id: bool, st) -> DecodedBatch:
         """cbx_decode_selected into column buffers sized by the selection's row count."""
         n_rec = sel["n"]
@@ -1256,6 +1299,32 @@ class FixedLenNestedReader(_BaseReader):
         self.check_binary_data_validity(len(data))
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
         return self.aggregate_by_device(t, len(data), group_by, aggregates, filters, max_groups)
+
+    def top_n_device(self, d_data, n_bytes: int, orders, limit: int, filters=None, first_record_id: int = 0,
+                     stream=None, max_workgroups: int = 0) -> DecodedBatch:
+        """Top-N / LIMIT pushdown over a split resident in HBM (`cobrix_amd.topn.SortOrder`s; SupportsPushDownTopN.
+        pushTopN, SupportsPushDownLimit.pushLimit with orders == []): of the rows `decode_device(..., filters=
+        filters)` would return, the min(limit, kept) rows that come first under `orders`, selected from the
+        record bytes by cbx_top_n_records and decoded IN SOURCE ORDER -- the pushdown is partial
+        (isPartiallyPushed), the caller orders the union of its batches (`cobrix_amd.topn.order_rows`).  Rows
+        equal on every key are taken by source position.  Raises `cobrix_amd.topn.Unhandled` (with the reason)
+        when a key or a filter cannot be evaluated exactly on the GPU.  The result does not depend on
+        max_workgroups (a bound on the select passes' grids; 0: the library's choice)."""
+        torch = _torch()
+        stride = self.get_record_size()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        sel = self._top_n_records(orders, limit, filters, d_data, n_bytes, n_bytes // stride, st, stride=stride,
+                                  first_record_id=first_record_id, max_workgroups=max_workgroups)
+        batch = self._decode_selection(d_data, n_bytes, sel, False, st)
+        batch.unhandled_filters = []
+        return batch
+
+    def top_n(self, data: bytes, orders, limit: int, filters=None, first_record_id: int = 0) -> DecodedBatch:
+        """`top_n_device` over host bytes, with the file-size checks of `decode`."""
+        torch = _torch()
+        self.check_binary_data_validity(len(data))
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        return self.top_n_device(t, len(data), orders, limit, filters, first_record_id)
 
     def get_row_iterator(self, data: bytes) -> Iterator[dict]:
         return iter(self.decode(data).to_rows())
@@ -2053,6 +2122,47 @@ class VarLenNestedReader(_BaseReader):
             entries = self.generate_index(t, len(data), off, ln, file_id)
         sel = self.select(t, vb, off, ln, entries, file_id)
         return self.aggregate_by_device(t, vb, sel, group_by, aggregates, filters, max_groups)
+
+    def top_n_device(self, d_data, n_bytes: int, sel_or_framing, orders, limit: int, filters=None,
+                     first_record_id: int = 0, file_id: int = 0, stream=None, max_workgroups: int = 0) -> DecodedBatch:
+        """Top-N / LIMIT pushdown (`cobrix_amd.topn.SortOrder`s; orders == []: the plain LIMIT) over a selection
+        (`select`'s result: record ids, segments and Seg_Id state carried over) or over framed records
+        ((rec_off, rec_len): Record_Id = first_record_id + index), restricted to the rows `filters` keep: the
+        min(limit, kept) rows that come first under `orders`, decoded IN SOURCE ORDER (the pushdown is partial:
+        the caller orders the union of its batches, `cobrix_amd.topn.order_rows`).  A reader with segment id
+        levels takes a selection only, as `filter`.  Raises `cobrix_amd.topn.Unhandled` when a key or a filter
+        cannot be evaluated exactly on the GPU; hierarchical reads refuse (rows are trees of segments)."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "Top-N on a hierarchical read: rows are trees of segments")
+        if isinstance(sel_or_framing, dict):
+            sel = self._top_n_records(orders, limit, filters, d_data, n_bytes, sel_or_framing["n"], st, sel=sel_or_framing,
+                                      max_workgroups=max_workgroups)
+        else:
+            if self.plan.seg_id_columns:
+                raise N.CbxError(N.CBX_E_ARGUMENT, "top_n: a reader with segment id levels takes a selection "
+                                                   "(the Seg_IdN state comes from select()); pass select()'s result")
+            rec_off, rec_len = sel_or_framing
+            sel = self._top_n_records(orders, limit, filters, d_data, n_bytes, int(rec_off.numel()), st, rec_off=rec_off,
+                                      rec_len=rec_len, first_record_id=first_record_id, file_id=file_id,
+                                      max_workgroups=max_workgroups)
+        return self.decode_selected(d_data, n_bytes, sel, stream)
+
+    def top_n(self, data: bytes, orders, limit: int, filters=None, file_id: int = 0,
+              input_file_name: Optional[str] = None) -> DecodedBatch:
+        """Top-N / LIMIT pushdown over a whole file: of the rows `read(data, filters=filters)` would return
+        (framing, sparse index, selection with segment_filter and file_end_offset, then the filters)."""
+        self._file_column(None, input_file_name, check_only=True)
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "Top-N on a hierarchical read: rows are trees of segments")
+        t = self._device_file(data)
+        off, ln, vb = self.frame_file(t, len(data))
+        entries = None
+        if self.index_generation_needed() and not self.params.is_text:
+            entries = self.generate_index(t, len(data), off, ln, file_id)
+        sel = self.select(t, vb, off, ln, entries, file_id)
+        return self._file_column(self.top_n_device(t, vb, sel, orders, limit, filters), input_file_name)
 
     def get_row_iterator(self, data: bytes) -> Iterator[dict]:
         return iter(self.read(data).to_rows())

@@ -673,6 +673,70 @@ int cbx_aggregate_grouped(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes
  * measured with HIP events on its stream while cbx_plan_set_profiling is on (zeros otherwise). */
 int cbx_group_pass_times(cbx_plan* plan, float* init_ms, float* accumulate_ms, float* emit_ms);
 
+/* ---- Top-N (ORDER BY .. LIMIT n) and LIMIT: an additive extension of ABI 25 ----
+ *
+ * SELECT .. WHERE filter ORDER BY k1 [DESC], .. LIMIT n, what SupportsPushDownTopN.pushTopN and
+ * SupportsPushDownLimit.pushLimit hand a data source.  No structure and no entry point above changes, so
+ * CBX_ABI_VERSION stays 25; a caller checks for the three entry points below.
+ * Of the rows `filter` keeps (NULL: every row) the call returns the min(limit, kept) rows that come first
+ * under `order`; rows equal on every key are taken by source position, the lower index first.  The rows are
+ * written IN SOURCE ORDER as a selection for cbx_decode_selected (record ids, active segment and seg_state
+ * carried as cbx_filter_records carries them): a caller that merges several batches, index entries or
+ * shards orders and limits the union itself (Spark: isPartiallyPushed() == true).  n_keys == 0 is the plain
+ * LIMIT: the first `limit` kept rows.  limit >= kept returns what cbx_filter_records returns.  The result
+ * does not depend on max_workgroups or on timing.
+ * Keys: up to CBX_TOPN_MAX_KEYS distinct fields.  A key's value is the column's output value exactly as the
+ * filter and the aggregates see it: a numeric key the signed value at the column's scale (128 bits for a
+ * precision above 18), a string key the UTF-8 bytes of the trimmed field through the plan's code page,
+ * compared as unsigned bytes (UTF8String.compareTo); a string cut by a short record orders as the cut
+ * value.  A key is NULL where the filter finds the field null.  Default per key: ascending, NULLS FIRST.
+ * Method (cbx_topn.h): an exact radix select over the records' composite sort key, 64 bits of it at a time.
+ * Workspace from the stream's pool: 8 bytes per source record (the current level's key words), two 64-bit
+ * words and two counts per 64 records, 2 bytes per record when the active segment comes from the plan's
+ * segment map, and 24 bytes per record of the tie class level 0 leaves (two buffers, allocated when a
+ * further level runs).  Host waits: one per level that runs (a level decides all but the records equal on
+ * its 64 bits; the last level is the source index, which always decides), plus one for the final count.
+ * limit == 0 or n_rec == 0 launches nothing.
+ * CBX_E_UNSUPPORTED (reason in cbx_last_error): whatever cbx_filter_records refuses for a field or in
+ * `filter`; a COMP-1 / COMP-2 key; a string key longer than 32 source bytes.  CBX_E_ARGUMENT: a malformed
+ * table, a repeated field, unknown flag bits, limit < 0, max_workgroups < 0, n_rec > INT32_MAX, the
+ * argument errors of cbx_filter_records (sources, Seg_Id levels without a selection, shared arrays). */
+#define CBX_TOPN_MAX_KEYS 4
+enum cbx_sort_flags { CBX_SORT_DESC = 1, CBX_SORT_NULLS_LAST = 2 };
+typedef struct {
+    int32_t field;         /* index into the plan's cbx_field table */
+    int32_t flags;         /* cbx_sort_flags bits */
+} cbx_sort_key;
+typedef struct {
+    int32_t n_keys;        /* 0 .. CBX_TOPN_MAX_KEYS */
+    int32_t reserved;
+    cbx_sort_key keys[CBX_TOPN_MAX_KEYS];
+} cbx_sort_order;
+typedef struct cbx_topn_info {
+    int64_t n_live;               /* rows the filter kept; -1 when the call launched nothing for limit == 0 */
+    int64_t ties_after_level0;    /* records equal to the threshold on the first 64 key bits that went to level 1 */
+    int64_t ties_max;             /* the largest tie class handed to a further level */
+    int64_t grid;                 /* workgroups of the select passes (0: no select ran) */
+    int32_t levels_run;           /* select levels run (0: limit >= n_rec, or nothing launched) */
+    int32_t levels_total;         /* 64-bit words of the composite key, the source index included */
+    int32_t words_per_key[CBX_TOPN_MAX_KEYS];   /* words of the composite key that hold bytes of key k */
+} cbx_topn_info;
+
+/* Sources (exactly one) and `out` as for cbx_filter_records.  max_workgroups bounds the grids of the select
+ * passes for a caller that shares the device (0: the library's choice). */
+int cbx_top_n_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                      const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                      int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                      const cbx_sort_order* order, int64_t limit, int32_t max_workgroups, cbx_selection* out,
+                      int64_t* n_selected, void* stream);
+
+/* How the plan's last Top-N call ran (host code only, no GPU work). */
+int cbx_top_n_info(cbx_plan* plan, cbx_topn_info* out);
+
+/* Durations in ms of the plan's last Top-N call: the key pass, the select levels (host waits between them
+ * included) and count + scan + emit, measured with HIP events while cbx_plan_set_profiling is on. */
+int cbx_top_n_pass_times(cbx_plan* plan, float* key_ms, float* select_ms, float* emit_ms);
+
 /* ---- the record walk with data-dependent offsets ----
  *
  * Layouts the static-offset tables above cannot express run through a per-record walk of the
