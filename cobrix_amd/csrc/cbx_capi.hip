@@ -30,6 +30,7 @@
 #include "cbx_aggregate.h"
 #include "cbx_group.h"
 #include "cbx_topn.h"
+#include "cbx_keyset.h"
 #include "cbx_gather.h"
 
 using namespace cbx;
@@ -2835,6 +2836,221 @@ extern "C" int cbx_top_n_pass_times(cbx_plan* P, float* key_ms, float* select_ms
     if (key_ms) *key_ms = P->topn_ms[0];
     if (select_ms) *select_ms = P->topn_ms[1];
     if (emit_ms) *emit_ms = P->topn_ms[2];
+    return CBX_OK;
+}
+
+// Key-set filters (cbx_keyset.h): a persistent device hash set of key values, and the filter stage with a test pass
+// that probes up to four of them.
+struct cbx_key_set {
+    const cbx_plan* plan = nullptr;
+    void* block = nullptr;        // program | header words | slot words | values | string bytes
+    KsTable t{};
+    const GrpProg* d_prog = nullptr;
+    cbx_keyset_info info{};
+};
+
+extern "C" int cbx_key_set_create(cbx_plan* P, const cbx_group_by* keys, const cbx_key_value* h_values, const uint8_t* h_bytes,
+                                  int32_t str_stride, const int32_t* str_off, int64_t n_values, void* stream,
+                                  cbx_key_set** out) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !keys || !out) return fail(CBX_E_ARGUMENT, "cbx_key_set_create: invalid arguments");
+    *out = nullptr;
+    std::vector<GrpProg> prog(1);
+    std::vector<AggProg> none(1);
+    memset(none.data(), 0, sizeof(AggProg));
+    std::string err;
+    int rb = group_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, keys, none[0], prog.data(), err);
+    if (rb != CBX_OK) return fail(rb, err);
+    KsLayout L;
+    rb = keyset_layout(P->hfields.data(), keys, n_values, str_stride, str_off, &L, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    if (n_values > 0 && (!h_values || (L.str_stride > 0 && !h_bytes)))
+        return fail(CBX_E_ARGUMENT, "cbx_key_set_create: value arrays required");
+    rb = keyset_check_values(prog[0], h_values, n_values, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    const int nk = prog[0].n_keys;
+    struct Guard {   // the block is the set's only device resource: freed on every error path
+        void* p = nullptr;
+        ~Guard() { if (p) (void)hipFree(p); }
+    } blk;
+    HIP_CHECK(hipMalloc(&blk.p, (size_t)L.device_bytes));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    uint64_t* hdr = (uint64_t*)(b8 + L.o_hdr);
+    uint64_t* slots = (uint64_t*)(b8 + L.o_slots);
+    HIP_CHECK(hipMemcpyAsync(b8, prog.data(), sizeof(GrpProg), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(hdr, 0, 64 + 8 * (size_t)L.capacity, st));   // header words and slot words are adjacent
+    if (n_values > 0) {
+        HIP_CHECK(hipMemcpyAsync(b8 + L.o_vals, h_values, sizeof(cbx_key_value) * (size_t)nk * (size_t)n_values, hipMemcpyHostToDevice, st));
+        if (L.str_stride > 0)
+            HIP_CHECK(hipMemcpyAsync(b8 + L.o_bytes, h_bytes, (size_t)L.str_stride * (size_t)n_values, hipMemcpyHostToDevice, st));
+    }
+    KsTable t{};
+    t.slots = slots;
+    t.vals = (const cbx_key_value*)(b8 + L.o_vals);
+    t.bytes = b8 + L.o_bytes;
+    t.capacity = (uint64_t)L.capacity;
+    t.n_values = n_values;
+    t.n_keys = nk;
+    t.str_stride = L.str_stride;
+    for (int k = 0; k < CBX_GROUP_MAX_KEYS; k++) t.str_off[k] = L.str_off[k];
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    const bool timed = P->profiling && n_values > 0;
+    if (timed) {
+        for (int k = 0; k < 2; k++) if (!(pe.e[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(pe.e[0], st));
+    }
+    if (n_values > 0)
+        hipLaunchKernelGGL(keyset_build_kernel, dim3(blocks_for(n_values, kKsBuildThreads)), dim3(kKsBuildThreads), 0, st, t,
+                           (const CBX_CONST GrpProg*)b8, slots, hdr);
+    if (timed) HIP_CHECK(hipEventRecord(pe.e[1], st));
+    HIP_CHECK(hipGetLastError());
+    uint64_t h[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    cbx_key_set* S = new cbx_key_set();
+    S->plan = P;
+    S->block = blk.p;
+    blk.p = nullptr;
+    S->t = t;
+    S->d_prog = (const GrpProg*)b8;
+    S->info.n_values = n_values;
+    S->info.n_distinct = (int64_t)h[0];
+    S->info.capacity = L.capacity;
+    S->info.device_bytes = L.device_bytes;
+    S->info.max_probe = (int64_t)h[1];
+    S->info.n_keys = nk;
+    if (timed && hipEventElapsedTime(&S->info.build_ms, pe.e[0], pe.e[1]) != hipSuccess) S->info.build_ms = 0.f;
+    *out = S;
+    return CBX_OK;
+}
+
+extern "C" int cbx_key_set_info(const cbx_key_set* S, cbx_keyset_info* out) {
+    if (!S || !out) return fail(CBX_E_ARGUMENT, "cbx_key_set_info: invalid arguments");
+    *out = S->info;
+    return CBX_OK;
+}
+
+extern "C" void cbx_key_set_destroy(cbx_key_set* S) {
+    if (!S) return;
+    if (S->block) (void)hipFree(S->block);
+    delete S;
+}
+
+// The filter stage with key sets: keyed test -> scan of the tile counts -> emit (the filter stage's own).
+extern "C" int cbx_filter_records_keyed(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                        const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                        int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                                        const cbx_key_set* const* sets, const int32_t* negate, int32_t n_sets,
+                                        cbx_selection* out, int64_t* n_selected, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !out || !n_selected || n_rec < 0 || n_bytes < 0 || start_offset < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records_keyed: invalid arguments");
+    *n_selected = 0;
+    P->flt_ms[0] = P->flt_ms[1] = P->flt_ms[2] = 0.f;
+    if (!sets || n_sets < 1 || n_sets > CBX_GROUP_MAX_KEYS)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records_keyed: 1 to " + std::to_string(CBX_GROUP_MAX_KEYS) + " key sets");
+    for (int s = 0; s < n_sets; s++) {
+        const std::string at = "cbx_filter_records_keyed: set " + std::to_string(s) + ": ";
+        if (!sets[s]) return fail(CBX_E_ARGUMENT, at + "null");
+        if (sets[s]->plan != P) return fail(CBX_E_ARGUMENT, at + "built on another plan");
+        if (negate && negate[s] != 0 && sets[s]->t.n_keys != 1)
+            return fail(CBX_E_ARGUMENT, at + "only a single-column set may be negated");
+    }
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records_keyed: exactly one source (selection, framed records, record stride)");
+    const int L = P->opts.has_segments ? P->opts.segments.n_levels : 0;
+    if (!in && L > 0)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records_keyed: a plan with Seg_Id levels filters a selection (cbx_select_records)");
+    struct Progs { FilterProg flt; KsDevSet sets[CBX_GROUP_MAX_KEYS]; };
+    std::vector<Progs> prog(1);
+    memset(prog.data(), 0, sizeof(Progs));
+    std::string err;
+    if (filter) {
+        const int rb = filter_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, filter, &prog[0].flt, err);
+        if (rb != CBX_OK) return fail(rb, err);
+    }
+    for (int s = 0; s < n_sets; s++) {
+        KsDevSet& d = prog[0].sets[s];
+        d.t = sets[s]->t;
+        d.grp = (const CBX_CONST GrpProg*)sets[s]->d_prog;
+        d.negate = negate && negate[s] != 0 ? 1 : 0;
+    }
+    if (in) out->file_id = in->file_id;   // (an empty selection carries the batch's File_Id too)
+    if (n_rec == 0) return CBX_OK;
+    if (!d_data || !out->rec_off || !out->rec_len || !out->record_id || !out->segment ||
+        (in && (!in->rec_off || !in->rec_len || !in->record_id || !in->segment)) ||
+        (in && L > 0 && (!in->seg_state || !out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records_keyed: selection arrays required");
+    if (in && (in->rec_off == out->rec_off || in->rec_len == out->rec_len || in->record_id == out->record_id ||
+               in->segment == out->segment || (L > 0 && in->seg_state == out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records_keyed: out must not share arrays with in");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_filter_records_keyed: n_rec records of rec_stride bytes exceed n_bytes");
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    const int64_t nb = scan_sums_len(n_tiles + 1);
+    // block: programs | keep words (n_tiles) | base (n_tiles + 1) | sums (nb) | counts (n_tiles + 1) | segments (n_rec)
+    const size_t o_keep = (sizeof(Progs) + 15) & ~(size_t)15;
+    const size_t o_base = o_keep + sizeof(uint64_t) * n_tiles;
+    const size_t o_sums = o_base + sizeof(int64_t) * (n_tiles + 1);
+    const size_t o_cnt = o_sums + sizeof(int64_t) * nb;
+    AsyncBlock blk(st);
+    const size_t o_seg = o_cnt + sizeof(uint32_t) * (n_tiles + 2);
+    const bool map_seg = !in && P->opts.has_segments;   // the active segment comes from the plan's segment map
+    HIP_CHECK(hipMallocAsync(&blk.p, o_seg + (map_seg ? sizeof(int16_t) * (size_t)n_rec : 0) + 16, st));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    int64_t* base = (int64_t*)(b8 + o_base);
+    int64_t* sums = (int64_t*)(b8 + o_sums);
+    uint32_t* counts = (uint32_t*)(b8 + o_cnt);
+    HIP_CHECK(hipMemcpyAsync(b8, prog.data(), sizeof(Progs), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(counts + n_tiles, 0, sizeof(uint32_t), st));
+    KsArgs g{};
+    FilterArgs& a = g.a;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = (const CBX_CONST FilterProg*)b8;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    a.keep = (uint64_t*)(b8 + o_keep);
+    a.counts = counts;
+    a.seg_out = map_seg ? (int16_t*)(b8 + o_seg) : nullptr;
+    g.has_filter = filter ? 1 : 0;
+    g.n_sets = n_sets;
+    g.sets = (const CBX_CONST KsDevSet*)(b8 + offsetof(Progs, sets));
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    hipEvent_t* ev = pe.e;
+    if (P->profiling) {
+        for (int k = 0; k < 4; k++) if (!(ev[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    const unsigned grid = blocks_for(n_tiles, kFltThreads / kWave);
+    hipLaunchKernelGGL(keyset_test_kernel, dim3(grid), dim3(kFltThreads), 0, st, g);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    device_scan(counts, n_tiles + 1, base, sums, st);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+    cbx_selection none{};
+    hipLaunchKernelGGL(filter_emit_kernel, dim3(grid), dim3(kFltThreads), 0, st, a, (const int64_t*)base, in ? *in : none,
+                       in ? 1 : 0, L > 0 ? 1 + L : 0, first_record_id, *out);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[3], st));
+    HIP_CHECK(hipGetLastError());
+    int64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, base + n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (P->profiling)
+        for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&P->flt_ms[k], ev[k], ev[k + 1]));
+    *n_selected = total;
     return CBX_OK;
 }
 

@@ -97,6 +97,19 @@ class Not(Filter):
     child: Filter
 
 
+@dataclass(frozen=True, eq=False)
+class InSet(Filter):
+    """(k1, .., kK) IN key_set: a `cobrix_amd.keyset.KeySet` built on the reader (`reader.key_set(names, values)`).
+    A row with a null key column is not kept."""
+    key_set: Any
+
+
+@dataclass(frozen=True, eq=False)
+class NotInSet(Filter):
+    """k NOT IN key_set (single-column sets).  A row with a null key is not kept."""
+    key_set: Any
+
+
 class Unhandled(Exception):
     """The filter cannot be evaluated exactly by the GPU stage (the reason is the message)."""
 
@@ -267,3 +280,65 @@ def compile_filters(plan, filters: Optional[Sequence[Filter]]) -> Tuple[Optional
             continue
         group += len(clauses)
     return (table if group > 0 else None), unhandled
+
+
+MAX_KEY_SETS = N.CBX_KEYSET_MAX_SETS
+
+
+def _has_set(flt: Filter) -> bool:
+    if isinstance(flt, (InSet, NotInSet)):
+        return True
+    if isinstance(flt, (And, Or)):
+        return _has_set(flt.left) or _has_set(flt.right)
+    return isinstance(flt, Not) and _has_set(flt.child)
+
+
+def _conjuncts(flt: Filter) -> List[Filter]:
+    """A top-level And that holds a set filter, as its AND-ed parts (others stay whole)."""
+    if isinstance(flt, And) and _has_set(flt):
+        return _conjuncts(flt.left) + _conjuncts(flt.right)
+    return [flt]
+
+
+def compile_filters_with_sets(plan, filters: Optional[Sequence[Filter]]):
+    """(table or None, sets, negate, unhandled): `compile_filters` plus the key-set filters of the conjunction, for
+    cbx_filter_records_keyed.  `sets` are the KeySet objects to probe, negate[i] != 0 for NOT IN.  Not(InSet) at
+    top level is NotInSet.  Returned unhandled, with the reason: a set filter under Or (or under a Not that is
+    not directly over it), a set past the stage's four, a negated set of more than one column, NotInSet over values
+    that held a null (the whole predicate is unknown), a set built on another reader's plan."""
+    sets: List[Any] = []
+    negate: List[int] = []
+    plain: List[Filter] = []
+    late = UnhandledFilters()
+    for top in filters or ():
+        for flt in _conjuncts(top):
+            f = flt
+            while isinstance(f, Not) and isinstance(f.child, Not):
+                f = f.child.child
+            if isinstance(f, Not) and isinstance(f.child, (InSet, NotInSet)):
+                f = NotInSet(f.child.key_set) if isinstance(f.child, InSet) else InSet(f.child.key_set)
+            if not isinstance(f, (InSet, NotInSet)):
+                if _has_set(f):
+                    late.add(flt, "a key-set filter under Or or under a negated group is not pushed down")
+                else:
+                    plain.append(flt)
+                continue
+            ks = f.key_set
+            if ks.closed:
+                raise ValueError("the key set is closed")
+            neg = isinstance(f, NotInSet)
+            if ks.plan is not plan:
+                late.add(flt, "the key set was built on another reader's plan")
+            elif neg and len(ks.names) != 1:
+                late.add(flt, "only a single-column key set may be negated")
+            elif neg and ks.has_null:
+                late.add(flt, "NotInSet over values that hold a null: the predicate is unknown for every row")
+            elif len(sets) >= MAX_KEY_SETS:
+                late.add(flt, f"more than {MAX_KEY_SETS} key sets in one filter call")
+            else:
+                sets.append(ks)
+                negate.append(1 if neg else 0)
+    table, unhandled = compile_filters(plan, plain)
+    for f, r in zip(late, late.reasons):
+        unhandled.add(f, r)
+    return table, sets, negate, unhandled

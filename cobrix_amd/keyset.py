@@ -1,0 +1,169 @@
+"""Key sets: a persistent hash set of key values on the device (`cbx_key_set_create`, include/cobrix_hip.h) for the
+filters `InSet` / `NotInSet` of `cobrix_amd.filter` -- the semi join of a fact file against the keys of a dimension,
+Spark's runtime `In` filters with hundreds to millions of values.
+
+A key value is what `GroupedAggregateResult` yields for a key column: int for an integral column, Decimal (or int)
+for a decimal one, str for a string column.  `compile_key_values` converts Python values with the exactness rules
+of the filter literals; a value the column can never hold (not representable at its scale, out of its range, a
+string longer than the field can produce) is dropped and counted, since it can never match; a tuple with a None is
+dropped as well (it can never match under three-valued logic) and remembered, because NOT IN over a null is unknown
+for every row.
+"""
+from __future__ import annotations
+
+import ctypes
+import decimal
+from dataclasses import dataclass
+from typing import Any, List, Optional, Sequence
+
+import numpy as np
+
+from . import aggregate as A
+from . import native as N
+from .filter import Unhandled
+
+
+@dataclass
+class CompiledKeyValues:
+    """The host arrays cbx_key_set_create takes."""
+    table: N.CbxGroupBy
+    keys: List[A.KeySlot]
+    values: np.ndarray          # uint8 [n_values * n_keys * sizeof(cbx_key_value)]
+    str_bytes: np.ndarray       # uint8 [n_values * str_stride]
+    str_stride: int
+    str_off: List[int]
+    n_values: int
+    dropped: int                # values no row can hold
+    has_null: bool              # a tuple held a None (dropped, not counted in `dropped`)
+
+
+_VALUE_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8"), ("str_len", "<i4"), ("reserved", "<i4")])
+assert _VALUE_DTYPE.itemsize == ctypes.sizeof(N.CbxKeyValue)
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _numeric(f: N.CbxField, v: Any, name: str) -> Optional[int]:
+    """The unscaled value at the column's scale; None when no row can hold it (filter._literal's rules)."""
+    if isinstance(v, bool) or not isinstance(v, (int, decimal.Decimal)):
+        raise Unhandled(f"{name}: key value {v!r} is not an int or Decimal (not exactly representable)")
+    d = decimal.Decimal(v)
+    if not d.is_finite():
+        raise Unhandled(f"{name}: key value {v!r} is not finite")
+    dec_col = f.out_type in (N.O_DEC64, N.O_DEC128)
+    with decimal.localcontext() as ctx:
+        ctx.prec = 200
+        u = d.scaleb(f.out_scale if dec_col else 0)
+        if u != u.to_integral_value():
+            return None
+        u = int(u)
+    if dec_col:
+        return u if abs(u) < 10 ** f.out_precision else None
+    bits = 31 if f.out_type == N.O_I32 else 63
+    return u if -(1 << bits) <= u < (1 << bits) else None
+
+
+def compile_key_values(plan, names: Sequence[str], tuples) -> CompiledKeyValues:
+    """The key columns `names` (what `compile_group_by` accepts, refused with its reasons) and the value tuples as the
+    library's host arrays.  A single key column also takes plain values instead of 1-tuples."""
+    names = list(names)
+    try:
+        table, keys = A.compile_group_by(plan, names)
+    except A.Unhandled as e:
+        raise Unhandled(str(e)) from None
+    nk = len(keys)
+    fields = [plan.fields[k.field] for k in keys]
+    str_off, off = [], 0
+    for k, f in zip(keys, fields):
+        str_off.append(off)
+        if k.is_str:
+            off += 3 * f.size
+    stride = off
+    rows, blobs = [], []
+    dropped, has_null = 0, False
+    for t in tuples:
+        if nk == 1 and not isinstance(t, (tuple, list)):
+            t = (t,)
+        if len(t) != nk:
+            raise ValueError(f"key value {t!r}: {nk} key columns take tuples of {nk}")
+        if any(v is None for v in t):
+            has_null = True
+            continue
+        cells, blob, ok = [], bytearray(stride), True
+        for k, f, name, v, so in zip(keys, fields, names, t, str_off):
+            if k.is_str:
+                if not isinstance(v, str):
+                    raise Unhandled(f"{name}: a string column takes str key values, not {type(v).__name__}")
+                b = v.encode("utf-8")
+                if len(v) > f.size or len(b) > 3 * f.size:
+                    ok = False
+                    break
+                blob[so:so + len(b)] = b
+                cells.append((0, 0, len(b), 0))
+            else:
+                u = _numeric(f, v, name)
+                if u is None:
+                    ok = False
+                    break
+                cells.append((u & _M64, (u >> 64) & _M64, 0, 0))
+        if not ok:
+            dropped += 1
+            continue
+        rows.extend(cells)
+        blobs.append(bytes(blob))
+    values = np.array(rows, dtype=_VALUE_DTYPE) if rows else np.zeros(0, dtype=_VALUE_DTYPE)
+    raw = np.frombuffer(b"".join(blobs), dtype=np.uint8) if stride and blobs else np.zeros(0, dtype=np.uint8)
+    return CompiledKeyValues(table, keys, values.view(np.uint8).reshape(-1), raw, stride, str_off, len(blobs), dropped, has_null)
+
+
+class KeySet:
+    """A device key set of one reader's plan.  Owns the library handle: `close()` (or the context manager) frees
+    the device memory; a closed set is refused by the filter compilation."""
+
+    def __init__(self, plan, plan_handle, names: Sequence[str], values, stream=None,
+                 compiled: Optional[CompiledKeyValues] = None):
+        c = compiled if compiled is not None else compile_key_values(plan, names, values)
+        self.plan = plan
+        self.names = list(names)
+        self.dropped = c.dropped
+        self.has_null = c.has_null
+        self.n_values = c.n_values
+        off = (ctypes.c_int32 * N.CBX_GROUP_MAX_KEYS)(*c.str_off)
+        h = ctypes.c_void_p()
+        self.handle = None
+        N.check(N.load().cbx_key_set_create(
+            plan_handle, ctypes.byref(c.table), c.values.ctypes.data if c.n_values else None,
+            c.str_bytes.ctypes.data if c.str_bytes.size else None, c.str_stride, ctypes.addressof(off), c.n_values,
+            ctypes.c_void_p(stream.cuda_stream if stream is not None else 0), ctypes.byref(h)))
+        self.handle = h
+
+    @property
+    def closed(self) -> bool:
+        return self.handle is None
+
+    def info(self) -> N.CbxKeysetInfo:
+        """n_values, n_distinct, capacity, device_bytes, max_probe, build_ms (profiling on) of the build."""
+        if self.closed:
+            raise ValueError("the key set is closed")
+        out = N.CbxKeysetInfo()
+        N.check(N.load().cbx_key_set_info(self.handle, ctypes.byref(out)))
+        return out
+
+    def close(self) -> None:
+        if self.handle is not None:
+            N.load().cbx_key_set_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self) -> "KeySet":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (interpreter shutdown)
+            pass
+
+    def __repr__(self) -> str:
+        return f"KeySet({self.names}, n_values={self.n_values}, dropped={self.dropped}, closed={self.closed})"

@@ -47,11 +47,14 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_filter_records", "cbx_filter_pass_times", "cbx_plan_direct_eligible", "cbx_plan_launch_info", "cbx_plan_walk_info",
                     "cbx_aggregate_records", "cbx_aggregate_pass_times",
                     "cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times",
-                    "cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times")
+                    "cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times",
+                    "cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed")
 # grouped aggregates were an additive extension of ABI 24: the symbols are required
 GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
 # Top-N / LIMIT pushdown was an additive extension of ABI 25: the symbols are required
 TOPN_SYMBOLS = ("cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times")
+# key-set filters were an additive extension of ABI 25: the symbols are required
+KEYSET_SYMBOLS = ("cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed")
 ABI_VERSION = 25
 
 
@@ -234,6 +237,22 @@ class CbxTopnInfo(ctypes.Structure):
                 ("words_per_key", ctypes.c_int32 * CBX_TOPN_MAX_KEYS)]
 
 
+# key sets (cbx_key_set): at most CBX_GROUP_MAX_KEYS key columns, at most CBX_GROUP_MAX_KEYS sets per keyed filter call
+CBX_KEYSET_MAX_SETS = CBX_GROUP_MAX_KEYS
+
+
+class CbxKeyValue(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64), ("str_len", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class CbxKeysetInfo(ctypes.Structure):
+    """cbx_key_set_info: what the build of a key set found."""
+    _fields_ = [("n_values", ctypes.c_int64), ("n_distinct", ctypes.c_int64), ("capacity", ctypes.c_int64),
+                ("device_bytes", ctypes.c_int64), ("max_probe", ctypes.c_int64), ("build_ms", ctypes.c_float),
+                ("n_keys", ctypes.c_int32)]
+
+
 W_GROUP, W_PRIM = 0, 1
 W_REDEFINED, W_REDEFINES = 0x1, 0x2
 
@@ -379,7 +398,11 @@ def load():
                      ("cbx_group_pass_times", [P, P, P, P]),
                      ("cbx_top_n_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, i64, i32, P, P, P]),
                      ("cbx_top_n_info", [P, P]),
-                     ("cbx_top_n_pass_times", [P, P, P, P])):
+                     ("cbx_top_n_pass_times", [P, P, P, P]),
+                     ("cbx_key_set_create", [P, P, P, P, i32, P, i64, P, ctypes.POINTER(P)]),
+                     ("cbx_key_set_info", [P, P]),
+                     ("cbx_key_set_destroy", [P]),
+                     ("cbx_filter_records_keyed", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, i32, P, P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):
@@ -392,6 +415,11 @@ def load():
     missing = [n for n in TOPN_SYMBOLS if not hasattr(L, n)]
     if missing and not os.environ.get("CBX_LIB_VARIANT"):
         raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (Top-N pushdown); rebuild it")
+    missing = [n for n in KEYSET_SYMBOLS if not hasattr(L, n)]
+    if missing and not os.environ.get("CBX_LIB_VARIANT"):
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (key-set filters); rebuild it")
+    if hasattr(L, "cbx_key_set_destroy"):
+        L.cbx_key_set_destroy.restype = None
     _lib = L
     return L
 

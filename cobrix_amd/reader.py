@@ -24,7 +24,8 @@ from . import native as N
 from .aggregate import (AggregateResult, GroupedAggregateResult, GroupOverflow, check_grouped_functions, compile_aggregates,
                         compile_group_by)
 from .aggregate import Unhandled as AggregateUnhandled
-from .filter import compile_filters
+from .filter import compile_filters_with_sets
+from .keyset import KeySet
 from .plan import DecodePlan, NativePlan, NeedsWalk, build_plan
 from .topn import compile_order
 from .schema import ST_DECIMAL, spark_schema
@@ -975,21 +976,53 @@ class _BaseReader:
         return sel, cs
 
     def _filter_records(self, table, d_data, n_bytes: int, n_rec: int, st, *, sel=None, rec_off=None, rec_len=None,
-                        stride: int = 0, first_record_id: int = 0, file_id: int = 0) -> Dict[str, Any]:
+                        stride: int = 0, first_record_id: int = 0, file_id: int = 0, sets=(), negate=()) -> Dict[str, Any]:
         """cbx_filter_records over one source (a selection, framed records, fixed-length records): the
-        surviving rows as a selection for cbx_decode_selected."""
+        surviving rows as a selection for cbx_decode_selected.  With key sets (`compile_filters_with_sets`) the
+        keyed entry point runs instead, `table` may then be None."""
         out, cs = self._empty_selection(n_rec, d_data.device)
         cs.file_id = sel["struct"].file_id if sel is not None else file_id
         ns = ctypes.c_int64(0)
-        N.check(N.load().cbx_filter_records(
-            self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
-            rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
-            n_rec, stride, self.params.start_offset, first_record_id, ctypes.byref(table), ctypes.byref(cs),
-            ctypes.byref(ns), ctypes.c_void_p(st.cuda_stream)))
+        head = (self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+                rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+                n_rec, stride, self.params.start_offset, first_record_id)
+        tail = (ctypes.byref(cs), ctypes.byref(ns), ctypes.c_void_p(st.cuda_stream))
+        if sets:
+            handles = (ctypes.c_void_p * len(sets))(*[s.handle for s in sets])
+            neg = (ctypes.c_int32 * len(sets))(*negate)
+            N.check(N.load().cbx_filter_records_keyed(*head, ctypes.byref(table) if table is not None else None,
+                                                      ctypes.addressof(handles), ctypes.addressof(neg), len(sets), *tail))
+        else:
+            N.check(N.load().cbx_filter_records(*head, ctypes.byref(table), *tail))
         out["n"] = ns.value
         out["struct"] = cs
         out["source"] = sel   # (the input selection's arrays stay alive with the result)
         return out
+
+    def key_set(self, names, values, stream=None) -> KeySet:
+        """A device key set over the key columns `names` (what GROUP BY accepts) from value tuples -- plain values
+        for one column -- for `filter.InSet` / `filter.NotInSet` in this reader's `filters=`.  The distinct keys of
+        `aggregate_by` on a dimension file are such tuples.  Close it (or use it as a context manager) to free the
+        device memory."""
+        return KeySet(self.plan, self.native.handle, names, values, stream)
+
+    def _pushed_filter(self, filters, d_data, n_bytes: int, n_rec: int, st, *, sel=None, rec_off=None, rec_len=None,
+                       stride: int = 0, first_record_id: int = 0, file_id: int = 0):
+        """The filter of an all-or-nothing stage (aggregates, GROUP BY, Top-N): (table or None, source) where source
+        holds the stage's n_rec / sel / rec_off / rec_len / stride.  Filters with key sets run the keyed filter
+        first and hand its selection to the stage as its `in` source; raises when a filter is not pushed down."""
+        src = dict(n_rec=n_rec, sel=sel, rec_off=rec_off, rec_len=rec_len, stride=stride)
+        if not filters:
+            return None, src
+        table, sets, negate, unhandled = compile_filters_with_sets(self.plan, filters)
+        if unhandled:
+            raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        if not sets:
+            return table, src
+        out = self._filter_records(table, d_data, n_bytes, n_rec, st, sel=sel, rec_off=rec_off, rec_len=rec_len,
+                                   stride=stride, first_record_id=first_record_id, file_id=file_id, sets=sets,
+                                   negate=negate)
+        return None, dict(n_rec=out["n"], sel=out, rec_off=None, rec_len=None, stride=0)
 
     def _aggregate_records(self, aggregates, filters, d_data, n_bytes: int, n_rec: int, st, *, sel=None, rec_off=None,
                            rec_len=None, stride: int = 0, max_workgroups: int = 0) -> AggregateResult:
@@ -997,11 +1030,9 @@ class _BaseReader:
         the full plan.  All or nothing: raises `cobrix_amd.aggregate.Unhandled` when a function cannot be
         pushed, or when a filter cannot be compiled (an aggregate over unfiltered rows would be wrong)."""
         table, slots = compile_aggregates(self.plan, aggregates)
-        flt = None
-        if filters:
-            flt, unhandled = compile_filters(self.plan, filters)
-            if unhandled:
-                raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        flt, src = self._pushed_filter(filters, d_data, n_bytes, n_rec, st, sel=sel, rec_off=rec_off, rec_len=rec_len,
+                                       stride=stride)
+        n_rec, sel, rec_off, rec_len, stride = src["n_rec"], src["sel"], src["rec_off"], src["rec_len"], src["stride"]
         res = N.CbxAggregateResult()
         N.check(N.load().cbx_aggregate_records(
             self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
@@ -1025,11 +1056,9 @@ class _BaseReader:
         gtable, keys = compile_group_by(self.plan, group_by)
         table, slots = compile_aggregates(self.plan, aggregates)
         check_grouped_functions(slots)
-        flt = None
-        if filters:
-            flt, unhandled = compile_filters(self.plan, filters)
-            if unhandled:
-                raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        flt, src = self._pushed_filter(filters, d_data, n_bytes, n_rec, st, sel=sel, rec_off=rec_off, rec_len=rec_len,
+                                       stride=stride)
+        n_rec, sel, rec_off, rec_len, stride = src["n_rec"], src["sel"], src["rec_off"], src["rec_len"], src["stride"]
         max_groups = int(max_groups)
         L = N.load()
         strides = N.CbxGroupStrides()
@@ -1070,11 +1099,9 @@ class _BaseReader:
         a key cannot be ordered on the GPU, or when a filter cannot be compiled (a Top-N over unfiltered rows
         would be wrong)."""
         table = compile_order(self.plan, orders)
-        flt = None
-        if filters:
-            flt, unhandled = compile_filters(self.plan, filters)
-            if unhandled:
-                raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        flt, src = self._pushed_filter(filters, d_data, n_bytes, n_rec, st, sel=sel, rec_off=rec_off, rec_len=rec_len,
+                                       stride=stride, first_record_id=first_record_id, file_id=file_id)
+        n_rec, sel, rec_off, rec_len, stride = src["n_rec"], src["sel"], src["rec_off"], src["rec_len"], src["stride"]
         limit = int(limit)
         out, cs = self._empty_selection(min(n_rec, max(limit, 0)), d_data.device)
         cs.file_id = sel["struct"].file_id if sel is not None else file_id
@@ -1182,10 +1209,10 @@ class FixedLenNestedReader(_BaseReader):
         st = stream if stream is not None else torch.cuda.current_stream()
         L = N.load()
         if filters:
-            table, unhandled = compile_filters(self.plan, filters)
-            if table is not None:
+            table, sets, negate, unhandled = compile_filters_with_sets(self.plan, filters)
+            if table is not None or sets:
                 sel = self._filter_records(table, d_data, n_bytes, n_rec, st, stride=stride,
-                                           first_record_id=first_record_id)
+                                           first_record_id=first_record_id, sets=sets, negate=negate)
                 batch = self._decode_selection(d_data, n_bytes, sel, False, st)
                 batch.unhandled_filters = unhandled
                 return batch
@@ -1562,23 +1589,25 @@ class VarLenNestedReader(_BaseReader):
         st = stream if stream is not None else torch.cuda.current_stream()
         if self.hierarchical:
             raise N.CbxError(N.CBX_E_UNSUPPORTED, "filters on a hierarchical read: dropping rows would break the tree")
-        table, unhandled = compile_filters(self.plan, filters)
+        table, sets, negate, unhandled = compile_filters_with_sets(self.plan, filters)
         is_sel = isinstance(sel_or_framing, dict)
         if not is_sel and self.plan.seg_id_columns:
             raise N.CbxError(N.CBX_E_ARGUMENT, "filter: a reader with segment id levels filters a selection "
                                                "(the Seg_IdN state comes from select()); pass select()'s result")
-        if table is None:
+        if table is None and not sets:
             if is_sel:
                 out = dict(sel_or_framing)
             else:   # no filter to evaluate: every framed record, as a selection
                 table = N.CbxFilter()
-        if table is not None:
+        if table is not None or sets:
             if is_sel:
-                out = self._filter_records(table, d_data, n_bytes, sel_or_framing["n"], st, sel=sel_or_framing)
+                out = self._filter_records(table, d_data, n_bytes, sel_or_framing["n"], st, sel=sel_or_framing,
+                                           sets=sets, negate=negate)
             else:
                 rec_off, rec_len = sel_or_framing
                 out = self._filter_records(table, d_data, n_bytes, int(rec_off.numel()), st, rec_off=rec_off,
-                                           rec_len=rec_len, first_record_id=first_record_id, file_id=file_id)
+                                           rec_len=rec_len, first_record_id=first_record_id, file_id=file_id,
+                                           sets=sets, negate=negate)
         out["unhandled"] = unhandled
         return out
 

@@ -737,6 +737,74 @@ int cbx_top_n_info(cbx_plan* plan, cbx_topn_info* out);
  * included) and count + scan + emit, measured with HIP events while cbx_plan_set_profiling is on. */
 int cbx_top_n_pass_times(cbx_plan* plan, float* key_ms, float* select_ms, float* emit_ms);
 
+/* ---- key-set filters (semi-join pushdown): an additive extension of ABI 25 ----
+ *
+ * WHERE (k1..kK) IN (<a set of tuples>) and WHERE k NOT IN (<a set of values>) for sets past the 64 literals of a
+ * cbx_filter: what Spark's dynamic partition pruning and runtime filters hand a relation as In sets of hundreds
+ * to millions of keys.  No structure and no entry point above changes, so CBX_ABI_VERSION stays 25; a caller
+ * checks for the four entry points below.
+ * A key set is built once over 1 to CBX_GROUP_MAX_KEYS distinct key fields of one plan from n_values >= 0 tuples
+ * of key values, lives on the device until it is destroyed, and is probed by any number of keyed filter calls
+ * of that plan on any stream.  A key value is exactly what the grouped aggregate emits for a group (cbx_group_key
+ * without the null flag): a numeric key the signed 128-bit value at the column's output scale, a string key the
+ * UTF-8 bytes of the trimmed field through the plan's code page.  The accepted and refused key fields are those
+ * of the grouped aggregate, with its reasons.  Duplicate tuples are one member; a set has no null member (a
+ * cbx_key_value has no null flag: what a null in the caller's list means is the caller's matter).
+ * The keyed filter keeps a record when all of these hold: its cbx_filter is true, if one is given; for every set
+ * with negate == 0 every key field of the record is non-null and the tuple is a member; for every set with
+ * negate != 0 the key is non-null and its value is not a member (single-column sets only).  A key is null exactly
+ * where the grouped aggregate makes it null, and a record with a null key component is kept by neither form (SQL
+ * three-valued logic: unknown is not true).  The result depends neither on the order of the values nor on timing.
+ * Table (cbx_keyset.h): open addressing with linear probing over `capacity` slots, the power of two at or above
+ * 2 * max(1, n_values); a slot is one 64-bit word, 0 when empty, else a 32-bit fingerprint of the key's hash in
+ * the high half and the value's index + 1 in the low half; the uploaded value array is the key storage. */
+typedef struct {
+    uint64_t lo, hi;       /* numeric key: 128-bit two's complement at the column's scale; zero for a string key */
+    int32_t str_len;       /* string key: UTF-8 bytes at h_bytes[v * str_stride + str_off[k]]; else 0 */
+    int32_t reserved;
+} cbx_key_value;
+typedef struct cbx_key_set cbx_key_set;
+typedef struct cbx_keyset_info {
+    int64_t n_values;      /* tuples given */
+    int64_t n_distinct;    /* members (duplicates are one) */
+    int64_t capacity;      /* slots of the table */
+    int64_t device_bytes;  /* device memory the set holds until it is destroyed */
+    int64_t max_probe;     /* the longest probe sequence of the build, in slots visited */
+    float build_ms;        /* the build launch, from HIP events while cbx_plan_set_profiling is on (else 0) */
+    int32_t n_keys;
+} cbx_keyset_info;
+
+/* Build a set over `keys` from host arrays: h_values[n_values][n_keys], and for string keys h_bytes[n_values]
+ * [str_stride] with key k's bytes at str_off[k], the layout cbx_group_layout reports for key_bytes (3 bytes per
+ * source byte of each string key; h_bytes and str_off may be NULL when no key is a string).  Uploads them and
+ * builds the table on `stream` (one lane per value: hash, probe, one device-scope 64-bit compare-and-swap per
+ * claim; an occupied slot with an equal fingerprint is compared against the occupant's tuple in the uploaded
+ * array), then waits for the stream, so the set may be probed from any stream afterwards.
+ * CBX_E_UNSUPPORTED (reason in cbx_last_error): a key field the grouped aggregate refuses.  CBX_E_ARGUMENT: a
+ * malformed key table, repeated or out-of-range fields, n_values < 0, a str_len below 0 or above 3 x the field
+ * size, strides other than the group layout's, device memory above CBX_GROUP_MAX_WORKSPACE_BYTES. */
+int cbx_key_set_create(cbx_plan* plan, const cbx_group_by* keys, const cbx_key_value* h_values, const uint8_t* h_bytes,
+                       int32_t str_stride, const int32_t* str_off, int64_t n_values, void* stream, cbx_key_set** out);
+
+/* What the build of the set found (host code only, no GPU work). */
+int cbx_key_set_info(const cbx_key_set* set, cbx_keyset_info* out);
+
+/* Frees the set's device memory; no call that probes it may still be running.  NULL is allowed. */
+void cbx_key_set_destroy(cbx_key_set* set);
+
+/* As cbx_filter_records (sources, `out`, *n_selected, the three passes and one host wait), with `filter` allowed
+ * to be NULL and 1 to CBX_GROUP_MAX_KEYS key sets: sets[s] is probed as IN when negate[s] == 0 and as NOT IN
+ * otherwise (negate == NULL: all IN).  The test pass evaluates the cbx_filter first and probes the sets for the
+ * lanes still kept: fingerprint before key, numerics as (hi, lo), strings streamed through the code page against
+ * the stored bytes.  n_rec == 0 launches nothing.  cbx_filter_pass_times reports this call's passes too.
+ * CBX_E_ARGUMENT: n_sets outside 1..4, a NULL set, a set built on another plan, a negated set of more than one
+ * column, and the argument errors of cbx_filter_records. */
+int cbx_filter_records_keyed(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                             const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                             int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                             const cbx_key_set* const* sets, const int32_t* negate, int32_t n_sets,
+                             cbx_selection* out, int64_t* n_selected, void* stream);
+
 /* ---- the record walk with data-dependent offsets ----
  *
  * Layouts the static-offset tables above cannot express run through a per-record walk of the
