@@ -2425,6 +2425,8 @@ extern "C" int cbx_filter_pass_times(cbx_plan* P, float* test_ms, float* scan_ms
     return CBX_OK;
 }
 
+extern "C" int32_t cbx_filter_max_op(void) { return CBX_OP_NOT_CONTAINS; }
+
 // Aggregate pushdown (cbx_aggregate.h): accumulate (grid-stride, one slab per workgroup) -> combine.
 extern "C" int cbx_aggregate_records(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
                                      const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,

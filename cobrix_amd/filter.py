@@ -8,7 +8,9 @@ one is returned unhandled with the reason, so nothing is dropped silently.
 
 Semantics (cbx_filter.h evaluates them on the record bytes): SQL three-valued logic, a row is kept only when
 the whole filter is true; numerics compare as the column's output value (int / long / the unscaled decimal at
-the column's scale), strings as the decoded UTF-8 bytes in unsigned byte order (UTF8String.compareTo).
+the column's scale), strings as the decoded UTF-8 bytes in unsigned byte order (UTF8String.compareTo);
+StringStartsWith / StringEndsWith / StringContains byte-wise over those bytes.  EqualNullSafe, AlwaysTrue and
+AlwaysFalse need no op of their own: they compile onto IS_NULL / EQ / NE and fold in `to_cnf`.
 """
 from __future__ import annotations
 
@@ -81,6 +83,35 @@ class StringStartsWith(Filter):
 
 
 @dataclass(frozen=True)
+class StringEndsWith(Filter):
+    attribute: str
+    value: str
+
+
+@dataclass(frozen=True)
+class StringContains(Filter):
+    attribute: str
+    value: str
+
+
+@dataclass(frozen=True)
+class EqualNullSafe(Filter):
+    """a <=> v: never unknown (null <=> null is true, null <=> v is false)."""
+    attribute: str
+    value: Any
+
+
+@dataclass(frozen=True)
+class AlwaysTrue(Filter):
+    pass
+
+
+@dataclass(frozen=True)
+class AlwaysFalse(Filter):
+    pass
+
+
+@dataclass(frozen=True)
 class And(Filter):
     left: Filter
     right: Filter
@@ -128,12 +159,14 @@ class UnhandledFilters(list):
 
 _LEAF_OP = {EqualTo: N.OP_EQ, GreaterThan: N.OP_GT, GreaterThanOrEqual: N.OP_GE, LessThan: N.OP_LT,
             LessThanOrEqual: N.OP_LE, In: N.OP_IN, IsNull: N.OP_IS_NULL, IsNotNull: N.OP_IS_NOT_NULL,
-            StringStartsWith: N.OP_STARTS_WITH}
+            StringStartsWith: N.OP_STARTS_WITH, StringEndsWith: N.OP_ENDS_WITH, StringContains: N.OP_CONTAINS}
+_STRING_ONLY_OPS = (N.OP_STARTS_WITH, N.OP_ENDS_WITH, N.OP_CONTAINS)
 # NOT over a leaf under three-valued logic: NOT(unknown) is unknown, and the negated op is unknown on null too
 _NEGATED = {N.OP_EQ: N.OP_NE, N.OP_NE: N.OP_EQ, N.OP_LT: N.OP_GE, N.OP_GE: N.OP_LT, N.OP_GT: N.OP_LE,
             N.OP_LE: N.OP_GT, N.OP_IN: N.OP_NOT_IN, N.OP_NOT_IN: N.OP_IN, N.OP_IS_NULL: N.OP_IS_NOT_NULL,
             N.OP_IS_NOT_NULL: N.OP_IS_NULL, N.OP_STARTS_WITH: N.OP_NOT_STARTS_WITH,
-            N.OP_NOT_STARTS_WITH: N.OP_STARTS_WITH}
+            N.OP_NOT_STARTS_WITH: N.OP_STARTS_WITH, N.OP_ENDS_WITH: N.OP_NOT_ENDS_WITH,
+            N.OP_NOT_ENDS_WITH: N.OP_ENDS_WITH, N.OP_CONTAINS: N.OP_NOT_CONTAINS, N.OP_NOT_CONTAINS: N.OP_CONTAINS}
 _STRING_KINDS = (N.K_STRING, N.K_STRING_ASCII)
 _NUMERIC_KINDS = (N.K_BCD, N.K_BINARY, N.K_ZONED, N.K_ASCII_NUM)
 
@@ -196,8 +229,8 @@ def _leaf(plan, flt: Filter) -> Leaf:
     elif f.kind not in _STRING_KINDS + _NUMERIC_KINDS:
         raise Unhandled(f"{name}: UTF-16, HEX and RAW fields are not filtered on the GPU")
     is_str = f.kind in _STRING_KINDS
-    if op == N.OP_STARTS_WITH and not is_str:
-        raise Unhandled(f"{name}: StringStartsWith on a numeric column")
+    if op in _STRING_ONLY_OPS and not is_str:
+        raise Unhandled(f"{name}: {type(flt).__name__} on a numeric column")
     if null_op:
         lits: Tuple[Any, ...] = ()
     elif op == N.OP_IN:
@@ -216,9 +249,20 @@ _MAX_CLAUSE_TERMS = 4 * N.CBX_FILTER_MAX_TERMS   # conversion stops early: the t
 
 def to_cnf(plan, flt: Filter, negate: bool = False) -> List[List[Leaf]]:
     """The filter as AND-ed clauses of OR-ed leaves: NOT pushed to the leaves (De Morgan, ops flipped), OR
-    distributed over AND.  Raises Unhandled."""
+    distributed over AND.  Constants fold here: true is no clause, false is one empty clause, which the AND
+    concatenation and the OR distribution below carry as they carry any other.  Raises Unhandled."""
     if isinstance(flt, Not):
         return to_cnf(plan, flt.child, not negate)
+    if isinstance(flt, (AlwaysTrue, AlwaysFalse)):
+        return [] if isinstance(flt, AlwaysTrue) != negate else [[]]
+    if isinstance(flt, EqualNullSafe):
+        # never unknown: NOT (a <=> v) is true on a null a, where NE is unknown
+        if flt.value is None:
+            return to_cnf(plan, IsNull(flt.attribute), negate)
+        eq = _leaf(plan, EqualTo(flt.attribute, flt.value))
+        if not negate:
+            return [[eq]]
+        return [[_leaf(plan, IsNull(flt.attribute)), Leaf(eq.field, N.OP_NE, eq.literals)]]
     if isinstance(flt, (And, Or)):
         a, b = to_cnf(plan, flt.left, negate), to_cnf(plan, flt.right, negate)
         if isinstance(flt, And) != negate:   # a conjunction (And, or a negated Or)
@@ -231,6 +275,15 @@ def to_cnf(plan, flt: Filter, negate: bool = False) -> List[List[Leaf]]:
         raise Unhandled(f"{type(flt).__name__} is not a pushed-down filter")
     leaf = _leaf(plan, flt)
     return [[Leaf(leaf.field, _NEGATED[leaf.op], leaf.literals) if negate else leaf]]
+
+
+def _false_leaf(plan) -> Leaf:
+    """A term no row satisfies, nulls included: IN over no literal, on the plan's first field the stage filters."""
+    if plan.walk is None:
+        for i, f in enumerate(plan.fields):
+            if f.n_dims == 0 and f.kind in _STRING_KINDS + _NUMERIC_KINDS:
+                return Leaf(i, N.OP_IN, ())
+    raise Unhandled("a constantly false filter needs a field the GPU stage filters, and the plan has none")
 
 
 def _append(table: N.CbxFilter, clauses: List[List[Leaf]], group: int) -> bool:
@@ -263,13 +316,16 @@ def _append(table: N.CbxFilter, clauses: List[List[Leaf]], group: int) -> bool:
 
 def compile_filters(plan, filters: Optional[Sequence[Filter]]) -> Tuple[Optional[N.CbxFilter], UnhandledFilters]:
     """(table or None, unhandled): the AND of `filters` as far as the GPU stage evaluates it exactly.  A filter is
-    compiled whole or returned unhandled; None when no filter was compiled."""
+    compiled whole or returned unhandled; None when no filter was compiled (a constantly true filter is handled
+    and adds nothing; a constantly false one is one IN term with no literal)."""
     table = N.CbxFilter()
     unhandled = UnhandledFilters()
     group = 0
     for flt in filters or ():
         try:
             clauses = to_cnf(plan, flt)
+            if any(not c for c in clauses):   # an empty clause: the filter is constantly false
+                clauses = [[_false_leaf(plan)]]
         except Unhandled as e:
             unhandled.add(flt, str(e))
             continue

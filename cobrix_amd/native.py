@@ -48,13 +48,16 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_aggregate_records", "cbx_aggregate_pass_times",
                     "cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times",
                     "cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times",
-                    "cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed")
+                    "cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed",
+                    "cbx_filter_max_op")
 # grouped aggregates were an additive extension of ABI 24: the symbols are required
 GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
 # Top-N / LIMIT pushdown was an additive extension of ABI 25: the symbols are required
 TOPN_SYMBOLS = ("cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times")
 # key-set filters were an additive extension of ABI 25: the symbols are required
 KEYSET_SYMBOLS = ("cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed")
+# suffix / substring filter ops were an additive extension of ABI 25: the symbol is required
+FILTER_STRING_SYMBOLS = ("cbx_filter_max_op",)
 ABI_VERSION = 25
 
 
@@ -138,7 +141,8 @@ class CbxSelection(ctypes.Structure):
 
 # row filters (cbx_filter): ops, table limits
 (OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_IN, OP_NOT_IN, OP_IS_NULL, OP_IS_NOT_NULL, OP_STARTS_WITH,
- OP_NOT_STARTS_WITH) = range(1, 13)
+ OP_NOT_STARTS_WITH, OP_ENDS_WITH, OP_NOT_ENDS_WITH, OP_CONTAINS, OP_NOT_CONTAINS) = range(1, 17)
+FILTER_MAX_OP = OP_NOT_CONTAINS   # what cbx_filter_max_op answers
 CBX_FILTER_MAX_TERMS, CBX_FILTER_MAX_LITERALS, CBX_FILTER_POOL_BYTES = 32, 64, 1024
 # the filter stage keeps one count per tile of 64 records and scans them in blocks of kScanTile counts
 # (cbx_kernels.hip: kScanBlock * kScanItems): a batch past FILTER_SCAN_BLOCK_RECORDS takes a second scan block
@@ -418,8 +422,14 @@ def load():
     missing = [n for n in KEYSET_SYMBOLS if not hasattr(L, n)]
     if missing and not os.environ.get("CBX_LIB_VARIANT"):
         raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (key-set filters); rebuild it")
+    missing = [n for n in FILTER_STRING_SYMBOLS if not hasattr(L, n)]
+    if missing and not os.environ.get("CBX_LIB_VARIANT"):
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (suffix / substring filter ops); rebuild it")
     if hasattr(L, "cbx_key_set_destroy"):
         L.cbx_key_set_destroy.restype = None
+    if hasattr(L, "cbx_filter_max_op"):
+        L.cbx_filter_max_op.argtypes = []
+        L.cbx_filter_max_op.restype = i32
     _lib = L
     return L
 

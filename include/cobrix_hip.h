@@ -489,7 +489,13 @@ enum cbx_filter_op {
     CBX_OP_EQ = 1, CBX_OP_NE = 2, CBX_OP_LT = 3, CBX_OP_LE = 4, CBX_OP_GT = 5, CBX_OP_GE = 6,
     CBX_OP_IN = 7, CBX_OP_NOT_IN = 8,              /* any / none of lit_count literals equal */
     CBX_OP_IS_NULL = 9, CBX_OP_IS_NOT_NULL = 10,   /* no literal */
-    CBX_OP_STARTS_WITH = 11, CBX_OP_NOT_STARTS_WITH = 12   /* strings, one literal */
+    CBX_OP_STARTS_WITH = 11, CBX_OP_NOT_STARTS_WITH = 12,  /* strings, one literal */
+    /* (additive extension of ABI 25; cbx_filter_max_op tells whether the library evaluates them)
+     * strings, one literal: the literal's bytes are a suffix of / occur in the decoded UTF-8 bytes, compared
+     * byte-wise as UTF8String.endsWith / contains do (a literal may begin or end inside a character).  An
+     * empty literal is true for every non-null value; a null value is unknown for the op and its negation. */
+    CBX_OP_ENDS_WITH = 13, CBX_OP_NOT_ENDS_WITH = 14,
+    CBX_OP_CONTAINS = 15, CBX_OP_NOT_CONTAINS = 16
 };
 typedef struct {
     uint64_t lo, hi;       /* numeric fields: two's complement 128-bit value at the field's output scale */
@@ -533,6 +539,11 @@ int cbx_filter_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, c
 /* Durations in ms of the three passes of the plan's last cbx_filter_records call, measured with HIP
  * events on its stream while cbx_plan_set_profiling is on (zeros otherwise). */
 int cbx_filter_pass_times(cbx_plan* plan, float* test_ms, float* scan_ms, float* emit_ms);
+
+/* The highest cbx_filter_op this library evaluates (16: CBX_OP_NOT_CONTAINS); a term with a higher op is
+ * CBX_E_ARGUMENT "unknown op".  ABI-25 libraries without this symbol evaluate ops up to
+ * CBX_OP_NOT_STARTS_WITH: enum values add no symbol, so this is how a caller tells the two apart. */
+int32_t cbx_filter_max_op(void);
 
 /* ---- aggregate pushdown ----
  *
