@@ -31,6 +31,7 @@
 #include "cbx_group.h"
 #include "cbx_topn.h"
 #include "cbx_keyset.h"
+#include "cbx_keyset_from.h"
 #include "cbx_gather.h"
 
 using namespace cbx;
@@ -2851,6 +2852,73 @@ struct cbx_key_set {
     cbx_keyset_info info{};
 };
 
+namespace {
+struct KeySetBlock {   // the block is the set's only device resource: freed on every error path
+    void* p = nullptr;
+    ~KeySetBlock() { if (p) (void)hipFree(p); }
+};
+
+// The set's block: program uploaded, header words and slot words zeroed (on st).
+int key_set_alloc(const GrpProg& prog, const KsLayout& L, hipStream_t st, KeySetBlock* blk) {
+    HIP_CHECK(hipMalloc(&blk->p, (size_t)L.device_bytes));
+    uint8_t* b8 = (uint8_t*)blk->p;
+    HIP_CHECK(hipMemcpyAsync(b8, &prog, sizeof(GrpProg), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(b8 + L.o_hdr, 0, 64 + 8 * (size_t)L.capacity, st));   // header words and slot words are adjacent
+    return CBX_OK;
+}
+
+// The build over the n_values tuples the block's value array holds (complete on st before this launch), the wait,
+// and the handle of plan P.  The events of a timed build come from plan E's pool.
+int key_set_finish(cbx_plan* P, cbx_plan* E, bool profiling, int nk, const KsLayout& L, KeySetBlock* blk, int64_t n_values,
+                   hipStream_t st, cbx_key_set** out) {
+    uint8_t* b8 = (uint8_t*)blk->p;
+    uint64_t* hdr = (uint64_t*)(b8 + L.o_hdr);
+    uint64_t* slots = (uint64_t*)(b8 + L.o_slots);
+    KsTable t{};
+    t.slots = slots;
+    t.vals = (const cbx_key_value*)(b8 + L.o_vals);
+    t.bytes = b8 + L.o_bytes;
+    t.capacity = (uint64_t)L.capacity;
+    t.n_values = n_values;
+    t.n_keys = nk;
+    t.str_stride = L.str_stride;
+    for (int k = 0; k < CBX_GROUP_MAX_KEYS; k++) t.str_off[k] = L.str_off[k];
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{E};
+    const bool timed = profiling && n_values > 0;
+    if (timed) {
+        for (int k = 0; k < 2; k++) if (!(pe.e[k] = take_event(E))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(pe.e[0], st));
+    }
+    if (n_values > 0)
+        hipLaunchKernelGGL(keyset_build_kernel, dim3(blocks_for(n_values, kKsBuildThreads)), dim3(kKsBuildThreads), 0, st, t,
+                           (const CBX_CONST GrpProg*)b8, slots, hdr);
+    if (timed) HIP_CHECK(hipEventRecord(pe.e[1], st));
+    HIP_CHECK(hipGetLastError());
+    uint64_t h[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    cbx_key_set* S = new cbx_key_set();
+    S->plan = P;
+    S->block = blk->p;
+    blk->p = nullptr;
+    S->t = t;
+    S->d_prog = (const GrpProg*)b8;
+    S->info.n_values = n_values;
+    S->info.n_distinct = (int64_t)h[0];
+    S->info.capacity = L.capacity;
+    S->info.device_bytes = L.device_bytes;
+    S->info.max_probe = (int64_t)h[1];
+    S->info.n_keys = nk;
+    if (timed && hipEventElapsedTime(&S->info.build_ms, pe.e[0], pe.e[1]) != hipSuccess) S->info.build_ms = 0.f;
+    *out = S;
+    return CBX_OK;
+}
+}  // namespace
+
 extern "C" int cbx_key_set_create(cbx_plan* P, const cbx_group_by* keys, const cbx_key_value* h_values, const uint8_t* h_bytes,
                                   int32_t str_stride, const int32_t* str_off, int64_t n_values, void* stream,
                                   cbx_key_set** out) {
@@ -2870,64 +2938,17 @@ extern "C" int cbx_key_set_create(cbx_plan* P, const cbx_group_by* keys, const c
         return fail(CBX_E_ARGUMENT, "cbx_key_set_create: value arrays required");
     rb = keyset_check_values(prog[0], h_values, n_values, err);
     if (rb != CBX_OK) return fail(rb, err);
-    const int nk = prog[0].n_keys;
-    struct Guard {   // the block is the set's only device resource: freed on every error path
-        void* p = nullptr;
-        ~Guard() { if (p) (void)hipFree(p); }
-    } blk;
-    HIP_CHECK(hipMalloc(&blk.p, (size_t)L.device_bytes));
+    KeySetBlock blk;
+    rb = key_set_alloc(prog[0], L, st, &blk);
+    if (rb != CBX_OK) return rb;
     uint8_t* b8 = (uint8_t*)blk.p;
-    uint64_t* hdr = (uint64_t*)(b8 + L.o_hdr);
-    uint64_t* slots = (uint64_t*)(b8 + L.o_slots);
-    HIP_CHECK(hipMemcpyAsync(b8, prog.data(), sizeof(GrpProg), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(hdr, 0, 64 + 8 * (size_t)L.capacity, st));   // header words and slot words are adjacent
+    const int nk = prog[0].n_keys;
     if (n_values > 0) {
         HIP_CHECK(hipMemcpyAsync(b8 + L.o_vals, h_values, sizeof(cbx_key_value) * (size_t)nk * (size_t)n_values, hipMemcpyHostToDevice, st));
         if (L.str_stride > 0)
             HIP_CHECK(hipMemcpyAsync(b8 + L.o_bytes, h_bytes, (size_t)L.str_stride * (size_t)n_values, hipMemcpyHostToDevice, st));
     }
-    KsTable t{};
-    t.slots = slots;
-    t.vals = (const cbx_key_value*)(b8 + L.o_vals);
-    t.bytes = b8 + L.o_bytes;
-    t.capacity = (uint64_t)L.capacity;
-    t.n_values = n_values;
-    t.n_keys = nk;
-    t.str_stride = L.str_stride;
-    for (int k = 0; k < CBX_GROUP_MAX_KEYS; k++) t.str_off[k] = L.str_off[k];
-    struct PassEvents {   // the events go back to the plan's pool on every exit path
-        cbx_plan* plan;
-        hipEvent_t e[2] = {nullptr, nullptr};
-        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
-    } pe{P};
-    const bool timed = P->profiling && n_values > 0;
-    if (timed) {
-        for (int k = 0; k < 2; k++) if (!(pe.e[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
-        HIP_CHECK(hipEventRecord(pe.e[0], st));
-    }
-    if (n_values > 0)
-        hipLaunchKernelGGL(keyset_build_kernel, dim3(blocks_for(n_values, kKsBuildThreads)), dim3(kKsBuildThreads), 0, st, t,
-                           (const CBX_CONST GrpProg*)b8, slots, hdr);
-    if (timed) HIP_CHECK(hipEventRecord(pe.e[1], st));
-    HIP_CHECK(hipGetLastError());
-    uint64_t h[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    cbx_key_set* S = new cbx_key_set();
-    S->plan = P;
-    S->block = blk.p;
-    blk.p = nullptr;
-    S->t = t;
-    S->d_prog = (const GrpProg*)b8;
-    S->info.n_values = n_values;
-    S->info.n_distinct = (int64_t)h[0];
-    S->info.capacity = L.capacity;
-    S->info.device_bytes = L.device_bytes;
-    S->info.max_probe = (int64_t)h[1];
-    S->info.n_keys = nk;
-    if (timed && hipEventElapsedTime(&S->info.build_ms, pe.e[0], pe.e[1]) != hipSuccess) S->info.build_ms = 0.f;
-    *out = S;
-    return CBX_OK;
+    return key_set_finish(P, P, P->profiling, nk, L, &blk, n_values, st, out);
 }
 
 extern "C" int cbx_key_set_info(const cbx_key_set* S, cbx_keyset_info* out) {
@@ -2940,6 +2961,137 @@ extern "C" void cbx_key_set_destroy(cbx_key_set* S) {
     if (!S) return;
     if (S->block) (void)hipFree(S->block);
     delete S;
+}
+
+// A key set from the records of a second file (cbx_keyset_from.h): distinct -> one host wait -> convert -> one host
+// wait -> cbx_key_set_create's build and wait.
+extern "C" int cbx_key_set_create_from_records(cbx_plan* P, const cbx_group_by* probe_keys, cbx_plan* Q,
+                                               const cbx_group_by* source_keys, const uint8_t* d_data, int64_t n_bytes,
+                                               const cbx_selection* in, const int64_t* d_rec_off, const int32_t* d_rec_len,
+                                               int64_t n_rec, int32_t rec_stride, int32_t start_offset,
+                                               const cbx_filter* source_filter, int64_t max_values, int32_t max_workgroups,
+                                               void* stream, cbx_key_set** out, cbx_keyset_source_info* info) {
+    hipStream_t st = (hipStream_t)stream;
+    const char* fn = "cbx_key_set_create_from_records: ";
+    if (out) *out = nullptr;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!P || !Q || !probe_keys || !source_keys || !out || n_rec < 0 || n_bytes < 0 || start_offset < 0 || max_workgroups < 0)
+        return fail(CBX_E_ARGUMENT, std::string(fn) + "invalid arguments");
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, std::string(fn) + "exactly one source (selection, framed records, record stride)");
+    struct Progs { KsfProg ksf; FilterProg flt; };
+    std::vector<Progs> progs(1);
+    std::vector<GrpProg> probe(1);
+    std::string err;
+    int rb = keyset_from_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, probe_keys, Q->hfields.data(),
+                               (int32_t)Q->hfields.size(), Q->walk, source_keys, probe.data(), &progs[0].ksf, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    if (source_filter) {
+        rb = filter_build(Q->hfields.data(), (int32_t)Q->hfields.size(), Q->walk, source_filter, &progs[0].flt, err);
+        if (rb != CBX_OK) return fail(rb, err);
+    }
+    int64_t cap = 0;
+    rb = keyset_from_capacity(max_values, &cap, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    const int nk = probe[0].n_keys;
+    int32_t str_off[CBX_GROUP_MAX_KEYS];   // the probe keys' group layout
+    const int32_t str_stride = keyset_from_strides(P->hfields.data(), probe_keys, probe[0], str_off);
+    KsLayout L;
+    rb = keyset_layout(P->hfields.data(), probe_keys, max_values, str_stride, str_off, &L, err);   // the largest set
+    if (rb != CBX_OK) return fail(rb, err);
+    const size_t o_hdr = (sizeof(Progs) + 63) & ~(size_t)63;
+    const size_t o_slots = o_hdr + 8 * KSF_WORDS;
+    const size_t total = o_slots + 8 * (size_t)cap;
+    if (info) { info->source_capacity = cap; info->workspace_bytes = (int64_t)total; }
+    KeySetBlock blk;
+    if (n_rec == 0) {
+        rb = keyset_layout(P->hfields.data(), probe_keys, 0, str_stride, str_off, &L, err);
+        if (rb != CBX_OK) return fail(rb, err);
+        rb = key_set_alloc(probe[0], L, st, &blk);
+        if (rb != CBX_OK) return rb;
+        return key_set_finish(P, Q, false, nk, L, &blk, 0, st, out);
+    }
+    if (!d_data || (in && (!in->rec_off || !in->rec_len || !in->segment)))
+        return fail(CBX_E_ARGUMENT, std::string(fn) + "data and selection arrays required");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, std::string(fn) + "n_rec records of rec_stride bytes exceed n_bytes");
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    int64_t grid = std::min<int64_t>((n_tiles + kFltThreads / kWave - 1) / (kFltThreads / kWave), (int64_t)Q->num_cus * 8);
+    if (max_workgroups > 0) grid = std::min<int64_t>(grid, max_workgroups);
+    // block (the stream's pool): programs | header words | slot words
+    AsyncBlock ws(st);
+    HIP_CHECK(hipMallocAsync(&ws.p, total, st));
+    uint8_t* b8 = (uint8_t*)ws.p;
+    HIP_CHECK(hipMemcpyAsync(b8, progs.data(), source_filter ? sizeof(Progs) : sizeof(KsfProg), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(b8 + o_hdr, 0, total - o_hdr, st));   // header words and slot words are adjacent
+    KsfArgs g{};
+    FilterArgs& a = g.a;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = source_filter ? (const CBX_CONST FilterProg*)(b8 + offsetof(Progs, flt)) : nullptr;
+    a.segmap = Q->opts.has_segments ? (const CBX_CONST cbx_segment_map*)Q->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)Q->d_fields;
+    a.lut = Q->d_lut;
+    g.prog = (const CBX_CONST KsfProg*)b8;
+    g.slots = (uint64_t*)(b8 + o_slots);
+    g.hdr = (uint64_t*)(b8 + o_hdr);
+    g.capacity = (uint64_t)cap;
+    g.max_values = max_values;
+    g.has_filter = source_filter ? 1 : 0;
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{Q};
+    hipEvent_t* ev = pe.e;
+    if (Q->profiling) {
+        for (int k = 0; k < 4; k++) if (!(ev[k] = take_event(Q))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    hipLaunchKernelGGL(keyset_distinct_kernel, dim3((unsigned)grid), dim3(kFltThreads), 0, st, g);
+    if (Q->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    HIP_CHECK(hipGetLastError());
+    uint64_t hdr[KSF_WORDS] = {};
+    HIP_CHECK(hipMemcpyAsync(hdr, g.hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));   // the claims size the set's block
+    if (Q->profiling && info) HIP_CHECK(hipEventElapsedTime(&info->distinct_ms, ev[0], ev[1]));
+    if (info) { info->n_rows = (int64_t)hdr[KSF_ROWS]; info->n_null_rows = (int64_t)hdr[KSF_NULL_ROWS]; }
+    if (hdr[KSF_OVERFLOW] != 0 || (int64_t)hdr[KSF_CLAIMS] > max_values) {
+        if (info) info->overflow = 1;
+        return fail(CBX_E_CAPACITY, std::string(fn) + "more than max_values (" + std::to_string(max_values) + ") distinct source keys");
+    }
+    const int64_t n_claims = (int64_t)hdr[KSF_CLAIMS];
+    rb = keyset_layout(P->hfields.data(), probe_keys, n_claims, str_stride, str_off, &L, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    rb = key_set_alloc(probe[0], L, st, &blk);
+    if (rb != CBX_OK) return rb;
+    int64_t n_values = 0, n_dropped = 0;
+    if (n_claims > 0) {
+        KsfOut o{};
+        o.vals = (cbx_key_value*)((uint8_t*)blk.p + L.o_vals);
+        o.bytes = (uint8_t*)blk.p + L.o_bytes;
+        o.n_keys = nk;
+        o.str_stride = L.str_stride;
+        for (int k = 0; k < CBX_GROUP_MAX_KEYS; k++) o.str_off[k] = L.str_off[k];
+        if (Q->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+        hipLaunchKernelGGL(keyset_convert_kernel, dim3(blocks_for(cap, kFltThreads)), dim3(kFltThreads), 0, st, g, o);
+        if (Q->profiling) HIP_CHECK(hipEventRecord(ev[3], st));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(hdr, g.hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));   // the build's launch takes the number of values
+        if (Q->profiling && info) HIP_CHECK(hipEventElapsedTime(&info->convert_ms, ev[2], ev[3]));
+        n_values = (int64_t)hdr[KSF_VALUES];
+        n_dropped = (int64_t)hdr[KSF_DROPPED];
+        if (n_values + n_dropped != n_claims)
+            return fail(CBX_E_STATE, std::string(fn) + "the convert pass did not see every claimed slot (internal error)");
+    }
+    if (info) { info->n_source_keys = n_claims; info->n_dropped = n_dropped; }
+    L.capacity = keyset_from_set_capacity(n_values);   // what cbx_key_set_create over these tuples would have chosen
+    return key_set_finish(P, Q, P->profiling || Q->profiling, nk, L, &blk, n_values, st, out);
 }
 
 // The filter stage with key sets: keyed test -> scan of the tile counts -> emit (the filter stage's own).

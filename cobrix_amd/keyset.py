@@ -115,9 +115,70 @@ def compile_key_values(plan, names: Sequence[str], tuples) -> CompiledKeyValues:
     return CompiledKeyValues(table, keys, values.view(np.uint8).reshape(-1), raw, stride, str_off, len(blobs), dropped, has_null)
 
 
+def _scale(k: A.KeySlot) -> int:
+    return k.out_scale if k.out_type in (N.O_DEC64, N.O_DEC128) else 0
+
+
+def compile_key_pairs(probe_plan, names: Sequence[str], source_plan, source_names: Sequence[str]):
+    """The key tables of a set of `probe_plan` over `names` built from the `source_names` columns of another file's
+    records (`cbx_key_set_create_from_records`): (probe table, source table).  Raises `Unhandled` with the reason:
+    what `compile_group_by` refuses on either side (prefixed with the side), a different number of columns, a string
+    column against a numeric one, a numeric pair of different scales (an integral column is scale 0; nothing is
+    rescaled on the device).  Precision, width, encoding and output type may differ."""
+    sides = []
+    for side, plan, cols in (("probe", probe_plan, names), ("source", source_plan, source_names)):
+        try:
+            sides.append(A.compile_group_by(plan, list(cols)))
+        except A.Unhandled as e:
+            raise Unhandled(f"{side}: {e}") from None
+    (ptable, pkeys), (stable, skeys) = sides
+    if len(pkeys) != len(skeys):
+        raise Unhandled(f"{len(pkeys)} probe key columns against {len(skeys)} source key columns")
+    for k, (a, b, an, bn) in enumerate(zip(pkeys, skeys, names, source_names)):
+        if a.is_str != b.is_str:
+            raise Unhandled(f"key {k}: a string column against a numeric one ({an} / {bn})")
+        if not a.is_str and _scale(a) != _scale(b):
+            raise Unhandled(f"key {k}: scales {_scale(a)} and {_scale(b)} differ ({an} / {bn})")
+    return ptable, stable
+
+
 class KeySet:
     """A device key set of one reader's plan.  Owns the library handle: `close()` (or the context manager) frees
     the device memory; a closed set is refused by the filter compilation."""
+
+    source_info: Optional[N.CbxKeysetSourceInfo] = None   # set by from_records
+
+    @classmethod
+    def from_records(cls, probe_plan, probe_handle, names: Sequence[str], source_plan, source_handle,
+                     source_names: Sequence[str], d_data_ptr: int, n_bytes: int, n_rec: int, *, sel_struct=None,
+                     rec_off_ptr=None, rec_len_ptr=None, stride: int = 0, start_offset: int = 0, filter_table=None,
+                     max_values: int = 65536, max_workgroups: int = 0, stream=None) -> "KeySet":
+        """A set of `probe_plan` over `names` built on the device from the `source_names` keys of another file's
+        records (one source: a selection struct, framed records or a record stride).  `dropped` counts the distinct
+        source keys the probe columns can never hold, `has_null` says whether a source row had a null key component
+        (such rows are never members), `source_info` holds the library's counts.  Raises `Unhandled` when the
+        columns do not pair and `GroupOverflow(max_values)` past max_values distinct source keys."""
+        ptable, stable = compile_key_pairs(probe_plan, names, source_plan, source_names)
+        info = N.CbxKeysetSourceInfo()
+        h = ctypes.c_void_p()
+        rc = N.load().cbx_key_set_create_from_records(
+            probe_handle, ctypes.byref(ptable), source_handle, ctypes.byref(stable), d_data_ptr, n_bytes,
+            ctypes.byref(sel_struct) if sel_struct is not None else None, rec_off_ptr, rec_len_ptr, n_rec, stride,
+            start_offset, ctypes.byref(filter_table) if filter_table is not None else None, int(max_values),
+            max_workgroups, ctypes.c_void_p(stream.cuda_stream if stream is not None else 0), ctypes.byref(h),
+            ctypes.byref(info))
+        if rc == N.CBX_E_CAPACITY and info.overflow:
+            raise A.GroupOverflow(int(max_values))
+        N.check(rc)
+        self = cls.__new__(cls)
+        self.plan = probe_plan
+        self.names = list(names)
+        self.dropped = info.n_dropped
+        self.has_null = info.n_null_rows > 0
+        self.n_values = info.n_source_keys - info.n_dropped
+        self.source_info = info
+        self.handle = h
+        return self
 
     def __init__(self, plan, plan_handle, names: Sequence[str], values, stream=None,
                  compiled: Optional[CompiledKeyValues] = None):

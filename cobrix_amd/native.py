@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times",
                     "cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times",
                     "cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed",
+                    "cbx_key_set_create_from_records",
                     "cbx_filter_max_op")
 # grouped aggregates were an additive extension of ABI 24: the symbols are required
 GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
@@ -56,6 +57,8 @@ GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_ti
 TOPN_SYMBOLS = ("cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times")
 # key-set filters were an additive extension of ABI 25: the symbols are required
 KEYSET_SYMBOLS = ("cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed")
+# key sets built from a second file's records were an additive extension of ABI 25: the symbol is required
+KEYSET_FROM_SYMBOLS = ("cbx_key_set_create_from_records",)
 # suffix / substring filter ops were an additive extension of ABI 25: the symbol is required
 FILTER_STRING_SYMBOLS = ("cbx_filter_max_op",)
 ABI_VERSION = 25
@@ -257,6 +260,14 @@ class CbxKeysetInfo(ctypes.Structure):
                 ("n_keys", ctypes.c_int32)]
 
 
+class CbxKeysetSourceInfo(ctypes.Structure):
+    """cbx_key_set_create_from_records: what the pass over the source records found."""
+    _fields_ = [("n_rows", ctypes.c_int64), ("n_null_rows", ctypes.c_int64), ("n_source_keys", ctypes.c_int64),
+                ("n_dropped", ctypes.c_int64), ("source_capacity", ctypes.c_int64), ("workspace_bytes", ctypes.c_int64),
+                ("overflow", ctypes.c_int32), ("reserved", ctypes.c_int32), ("distinct_ms", ctypes.c_float),
+                ("convert_ms", ctypes.c_float)]
+
+
 W_GROUP, W_PRIM = 0, 1
 W_REDEFINED, W_REDEFINES = 0x1, 0x2
 
@@ -406,7 +417,9 @@ def load():
                      ("cbx_key_set_create", [P, P, P, P, i32, P, i64, P, ctypes.POINTER(P)]),
                      ("cbx_key_set_info", [P, P]),
                      ("cbx_key_set_destroy", [P]),
-                     ("cbx_filter_records_keyed", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, i32, P, P, P])):
+                     ("cbx_filter_records_keyed", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, i32, P, P, P]),
+                     ("cbx_key_set_create_from_records", [P, P, P, P, P, i64, P, P, P, i64, i32, i32, P, i64, i32, P,
+                                                          ctypes.POINTER(P), P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):
@@ -422,6 +435,9 @@ def load():
     missing = [n for n in KEYSET_SYMBOLS if not hasattr(L, n)]
     if missing and not os.environ.get("CBX_LIB_VARIANT"):
         raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (key-set filters); rebuild it")
+    missing = [n for n in KEYSET_FROM_SYMBOLS if not hasattr(L, n)]
+    if missing and not os.environ.get("CBX_LIB_VARIANT"):
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (key sets from records); rebuild it")
     missing = [n for n in FILTER_STRING_SYMBOLS if not hasattr(L, n)]
     if missing and not os.environ.get("CBX_LIB_VARIANT"):
         raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (suffix / substring filter ops); rebuild it")

@@ -1084,6 +1084,26 @@ class _BaseReader:
             return hdr.n_groups, hdr.n_rows
         return GroupedAggregateResult.from_arrays(table, slots, keys, strides, hdr.n_groups, n_rows, values, cells, key_bytes)
 
+    def _key_set_from(self, source_names, probe, names, filters, max_values: int, d_data, n_bytes: int, n_rec: int, st, *,
+                      sel=None, rec_off=None, rec_len=None, stride: int = 0, file_id: int = 0,
+                      max_workgroups: int = 0) -> KeySet:
+        """cbx_key_set_create_from_records with this reader as the source: the set of reader `probe` over `names`
+        (default: source_names) from the distinct `source_names` keys of the rows `filters` keep.  All or nothing as
+        `_aggregate_grouped`: a filter that is not pushed down raises (a set over unfiltered rows would be wrong);
+        filters with key sets of this reader run the keyed filter first, which chains semi joins."""
+        source_names = list(source_names)
+        names = list(names) if names is not None else source_names
+        flt, src = self._pushed_filter(filters, d_data, n_bytes, n_rec, st, sel=sel, rec_off=rec_off, rec_len=rec_len,
+                                       stride=stride, file_id=file_id)
+        n_rec, sel, rec_off, rec_len, stride = src["n_rec"], src["sel"], src["rec_off"], src["rec_len"], src["stride"]
+        return KeySet.from_records(
+            probe.plan, probe.native.handle, names, self.plan, self.native.handle, source_names, d_data.data_ptr(), n_bytes,
+            n_rec, sel_struct=sel["struct"] if sel is not None else None,
+            rec_off_ptr=rec_off.data_ptr() if rec_off is not None else None,
+            rec_len_ptr=rec_len.data_ptr() if rec_len is not None else None, stride=stride,
+            start_offset=self.params.start_offset, filter_table=flt, max_values=max_values, max_workgroups=max_workgroups,
+            stream=st)
+
     def group_pass_times(self) -> Tuple[float, float, float]:
         """(init, accumulate, emit) ms of the last grouped aggregate call (cbx_plan_set_profiling on; zeros otherwise)."""
         i, a, e = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
@@ -1326,6 +1346,29 @@ class FixedLenNestedReader(_BaseReader):
         self.check_binary_data_validity(len(data))
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
         return self.aggregate_by_device(t, len(data), group_by, aggregates, filters, max_groups)
+
+    def key_set_of_device(self, d_data, n_bytes: int, source_names, probe, names=None, filters=None, max_values: int = 65536,
+                          stream=None, max_workgroups: int = 0) -> KeySet:
+        """A key set of reader `probe` over its columns `names` (default: source_names), built on the device from the
+        distinct `source_names` keys of this reader's rows that `filters` keep -- the semi join of `probe`'s file
+        against this (dimension) file, for `filter.InSet` / `filter.NotInSet` in `probe`'s `filters=`.  The columns
+        pair by position: string with string, numeric with numeric of the same scale; encodings, widths and code
+        pages may differ (`keyset.compile_key_pairs`).  Rows with a null key are never members (`has_null`), keys the
+        probe columns cannot hold are left out (`dropped`).  Raises `filter.Unhandled` when the columns do not pair,
+        `aggregate.Unhandled` when a filter is not pushed down and `aggregate.GroupOverflow` past max_values
+        distinct source keys."""
+        torch = _torch()
+        stride = self.get_record_size()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        return self._key_set_from(source_names, probe, names, filters, max_values, d_data, n_bytes, n_bytes // stride, st,
+                                  stride=stride, max_workgroups=max_workgroups)
+
+    def key_set_of(self, data: bytes, source_names, probe, names=None, filters=None, max_values: int = 65536) -> KeySet:
+        """`key_set_of_device` over host bytes, with the file-size checks of `decode`."""
+        torch = _torch()
+        self.check_binary_data_validity(len(data))
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        return self.key_set_of_device(t, len(data), source_names, probe, names, filters, max_values)
 
     def top_n_device(self, d_data, n_bytes: int, orders, limit: int, filters=None, first_record_id: int = 0,
                      stream=None, max_workgroups: int = 0) -> DecodedBatch:
@@ -2151,6 +2194,37 @@ class VarLenNestedReader(_BaseReader):
             entries = self.generate_index(t, len(data), off, ln, file_id)
         sel = self.select(t, vb, off, ln, entries, file_id)
         return self.aggregate_by_device(t, vb, sel, group_by, aggregates, filters, max_groups)
+
+    def key_set_of_device(self, d_data, n_bytes: int, sel_or_framing, source_names, probe, names=None, filters=None,
+                          max_values: int = 65536, file_id: int = 0, stream=None, max_workgroups: int = 0) -> KeySet:
+        """A key set of reader `probe` over its columns `names` (default: source_names), built on the device from the
+        distinct `source_names` keys of a selection or of framed records of this reader (as `aggregate_by_device`)
+        that `filters` keep; see `FixedLenNestedReader.key_set_of_device`.  A key inside an inactive segment
+        redefine is null."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "key sets of a hierarchical read: rows are trees of segments")
+        if isinstance(sel_or_framing, dict):
+            return self._key_set_from(source_names, probe, names, filters, max_values, d_data, n_bytes, sel_or_framing["n"],
+                                      st, sel=sel_or_framing, file_id=file_id, max_workgroups=max_workgroups)
+        rec_off, rec_len = sel_or_framing
+        return self._key_set_from(source_names, probe, names, filters, max_values, d_data, n_bytes, int(rec_off.numel()), st,
+                                  rec_off=rec_off, rec_len=rec_len, file_id=file_id, max_workgroups=max_workgroups)
+
+    def key_set_of(self, data: bytes, source_names, probe, names=None, filters=None, max_values: int = 65536,
+                   file_id: int = 0) -> KeySet:
+        """`key_set_of_device` over a whole file: the row set of `aggregate` (framing, sparse index, selection with
+        segment_filter and file_end_offset, then the filters)."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "key sets of a hierarchical read: rows are trees of segments")
+        t = self._device_file(data)
+        off, ln, vb = self.frame_file(t, len(data))
+        entries = None
+        if self.index_generation_needed() and not self.params.is_text:
+            entries = self.generate_index(t, len(data), off, ln, file_id)
+        sel = self.select(t, vb, off, ln, entries, file_id)
+        return self.key_set_of_device(t, vb, sel, source_names, probe, names, filters, max_values, file_id)
 
     def top_n_device(self, d_data, n_bytes: int, sel_or_framing, orders, limit: int, filters=None,
                      first_record_id: int = 0, file_id: int = 0, stream=None, max_workgroups: int = 0) -> DecodedBatch:

@@ -816,6 +816,59 @@ int cbx_filter_records_keyed(cbx_plan* plan, const uint8_t* d_data, int64_t n_by
                              const cbx_key_set* const* sets, const int32_t* negate, int32_t n_sets,
                              cbx_selection* out, int64_t* n_selected, void* stream);
 
+/* ---- key sets built from the records of a second file: an additive extension of ABI 25 ----
+ *
+ * The semi join of a fact file against the keys of a dimension file without a trip of the keys through the host:
+ * the set of `probe_plan` over `probe_keys` is built on the device from the `source_keys` of the records of a
+ * second file, read through `source_plan` (its own copybook, code page, trimming policy and row filter).  No
+ * structure and no entry point above changes, so CBX_ABI_VERSION stays 25; a caller checks for the symbol.
+ * Over decoded values: take the source rows `source_filter` keeps (NULL: all; the record sources are those of
+ * cbx_aggregate_grouped -- a selection, framed records or fixed-length records, exactly one); decode the
+ * source_keys tuple of each as the grouped aggregate does; skip tuples with a NULL component (n_null_rows counts
+ * those rows); take the distinct tuples that remain (n_source_keys); keep the ones the probe_keys columns can hold
+ * (the others are counted in n_dropped: a decimal probe column holds |v| < 10^precision, an integer one the signed
+ * 32- / 64-bit range, a string one at most 3 x its size in UTF-8 bytes and at most its size in characters).  The
+ * set is what cbx_key_set_create(probe_plan, probe_keys, <those tuples>) builds: it belongs to probe_plan, and
+ * cbx_key_set_info, cbx_key_set_destroy and cbx_filter_records_keyed treat it like any other set (its
+ * capacity is the one of n_values tuples; only device_bytes may be larger, the block being laid out for
+ * n_source_keys tuples before the drops are known).  cbx_keyset_info.n_values is n_source_keys - n_dropped; the order of the
+ * values in the device array is unspecified.  Members, n_distinct and the four counts depend neither on
+ * max_workgroups (a bound on the distinct pass's grid; 0: the library's choice) nor on timing.
+ * Columns, checked before anything is launched: both key tables have the same n_keys; each pair is string / string
+ * or numeric / numeric (else CBX_E_ARGUMENT); a numeric pair has one output scale, an integral column counting as
+ * scale 0 -- precision, width, encoding and output type may differ, since the canonical key is the signed 128-bit
+ * value at the column's scale (different scales: CBX_E_UNSUPPORTED, "key k: scales 2 and 3 differ"; nothing is
+ * rescaled on the device).  Each side is otherwise refused as the grouped aggregate refuses a key, the reason
+ * prefixed with "probe: " or "source: ".  A string key is the UTF-8 bytes of the trimmed source field through the
+ * SOURCE plan's code page and trimming policy, compared as bytes with what the probe plan makes of its own field.
+ * max_values >= 1 bounds the distinct source keys: with more, the call returns CBX_E_CAPACITY, sets
+ * info->overflow, leaves *out NULL and holds no device memory (a partial set would silently drop rows of the
+ * join).  The distinct table (cbx_keyset_from.h) has source_capacity = the power of two >= 2 * max_values slots of
+ * 8 bytes, taken from the stream's memory pool and returned before the call ends; CBX_E_ARGUMENT when it or the
+ * set's block for max_values values would exceed CBX_GROUP_MAX_WORKSPACE_BYTES.  n_rec == 0 launches no pass over
+ * records and gives an empty set.
+ * Passes: distinct (one pass over the source records: filter, key hash, find or claim a slot of bare 64-bit words),
+ * convert (one lane per slot: the representative's key, the probe columns' limits, a dense index into the new set's
+ * value array), then cbx_key_set_create's build over that array.  Host waits: three -- after the distinct pass (it
+ * sizes the set's block), after the convert pass (the number of values the build takes), and the build's own. */
+typedef struct cbx_keyset_source_info {
+    int64_t n_rows;        /* source records the source filter kept */
+    int64_t n_null_rows;   /* of those, records with a null key component (never members) */
+    int64_t n_source_keys; /* distinct non-null source key tuples */
+    int64_t n_dropped;     /* of those, tuples the probe columns can never hold (not members) */
+    int64_t source_capacity, workspace_bytes;  /* the distinct table: slots, bytes from the stream's pool */
+    int32_t overflow;      /* more than max_values distinct source keys: no set was built */
+    int32_t reserved;
+    float distinct_ms, convert_ms;   /* HIP events while cbx_plan_set_profiling(source_plan) is on, else 0 */
+} cbx_keyset_source_info;
+
+int cbx_key_set_create_from_records(cbx_plan* probe_plan, const cbx_group_by* probe_keys, cbx_plan* source_plan,
+                                    const cbx_group_by* source_keys, const uint8_t* d_data, int64_t n_bytes,
+                                    const cbx_selection* in, const int64_t* d_rec_off, const int32_t* d_rec_len,
+                                    int64_t n_rec, int32_t rec_stride, int32_t start_offset,
+                                    const cbx_filter* source_filter, int64_t max_values, int32_t max_workgroups,
+                                    void* stream, cbx_key_set** out, cbx_keyset_source_info* info /* may be NULL */);
+
 /* ---- the record walk with data-dependent offsets ----
  *
  * Layouts the static-offset tables above cannot express run through a per-record walk of the
