@@ -32,6 +32,7 @@
 #include "cbx_topn.h"
 #include "cbx_keyset.h"
 #include "cbx_keyset_from.h"
+#include "cbx_keymap.h"
 #include "cbx_gather.h"
 
 using namespace cbx;
@@ -176,6 +177,7 @@ struct cbx_plan {
     struct CallEvents { hipEvent_t e[3]; };
     std::vector<CallEvents> ev_calls;    // recorded, not yet read
     float flt_ms[3] = {0.f, 0.f, 0.f};   // test / scan / emit of the last cbx_filter_records call (profiling)
+    float join_ms[3] = {0.f, 0.f, 0.f};  // test / scan / emit of the last cbx_join_records call (profiling)
     float grp_ms[3] = {0.f, 0.f, 0.f};   // init / accumulate / emit of the last cbx_aggregate_grouped call (profiling)
     float agg_ms[2] = {0.f, 0.f};        // accumulate / combine of the last cbx_aggregate_records call (profiling)
     float topn_ms[3] = {0.f, 0.f, 0.f};  // key / select / emit of the last cbx_top_n_records call (profiling)
@@ -3205,6 +3207,317 @@ extern "C" int cbx_filter_records_keyed(cbx_plan* P, const uint8_t* d_data, int6
     if (P->profiling)
         for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&P->flt_ms[k], ev[k], ev[k + 1]));
     *n_selected = total;
+    return CBX_OK;
+}
+
+// Lookup joins (cbx_keymap.h): a key map is the set of cbx_key_set_create_from_records plus first_row / n_rows per
+// value; the join stage is the keyed filter stage with the map probe in its test pass.
+struct cbx_key_map {
+    const cbx_plan* plan = nullptr;   // the probe plan
+    cbx_key_set* set = nullptr;       // owned
+    void* payload = nullptr;          // first_row (n_values) | n_rows (n_values)
+    int64_t* first_row = nullptr;
+    int64_t* n_rows = nullptr;
+    cbx_keymap_info info{};
+};
+
+extern "C" void cbx_key_map_destroy(cbx_key_map* M) {
+    if (!M) return;
+    if (M->payload) (void)hipFree(M->payload);
+    cbx_key_set_destroy(M->set);
+    delete M;
+}
+
+extern "C" int cbx_key_map_info(const cbx_key_map* M, cbx_keymap_info* out) {
+    if (!M || !out) return fail(CBX_E_ARGUMENT, "cbx_key_map_info: invalid arguments");
+    *out = M->info;
+    return CBX_OK;
+}
+
+extern "C" const cbx_key_set* cbx_key_map_set(const cbx_key_map* M) { return M ? M->set : nullptr; }
+
+// The set (its three waits), then init + fill + stats over the same source and one more wait.
+extern "C" int cbx_key_map_create_from_records(cbx_plan* P, const cbx_group_by* probe_keys, cbx_plan* Q,
+                                               const cbx_group_by* source_keys, const uint8_t* d_data, int64_t n_bytes,
+                                               const cbx_selection* in, const int64_t* d_rec_off, const int32_t* d_rec_len,
+                                               int64_t n_rec, int32_t rec_stride, int32_t start_offset,
+                                               const cbx_filter* source_filter, int64_t max_values, int32_t max_workgroups,
+                                               void* stream, cbx_key_map** out, cbx_keymap_info* info) {
+    hipStream_t st = (hipStream_t)stream;
+    if (out) *out = nullptr;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!out) return fail(CBX_E_ARGUMENT, "cbx_key_map_create_from_records: invalid arguments");
+    cbx_keyset_source_info si{};
+    cbx_key_set* S = nullptr;
+    int rb = cbx_key_set_create_from_records(P, probe_keys, Q, source_keys, d_data, n_bytes, in, d_rec_off, d_rec_len, n_rec,
+                                             rec_stride, start_offset, source_filter, max_values, max_workgroups, stream, &S, &si);
+    cbx_keymap_info mi{};
+    mi.n_rows = si.n_rows; mi.n_null_rows = si.n_null_rows; mi.n_source_keys = si.n_source_keys; mi.n_dropped = si.n_dropped;
+    mi.source_capacity = si.source_capacity; mi.workspace_bytes = si.workspace_bytes; mi.overflow = si.overflow;
+    mi.distinct_ms = si.distinct_ms; mi.convert_ms = si.convert_ms;
+    if (info) *info = mi;
+    if (rb != CBX_OK) return rb;
+    struct MapGuard {   // the map's device memory is freed on every error path
+        cbx_key_map* m;
+        ~MapGuard() { cbx_key_map_destroy(m); }
+    } guard{new cbx_key_map()};
+    cbx_key_map* M = guard.m;
+    M->plan = P;
+    M->set = S;
+    M->info = mi;
+    const int64_t nv = S->t.n_values;
+    if (nv > 0 && n_rec > 0) {
+        HIP_CHECK(hipMalloc(&M->payload, 16 * (size_t)nv));
+        M->first_row = (int64_t*)M->payload;
+        M->n_rows = M->first_row + nv;
+        // (the set's call checked every argument; the programs are built again, which cannot fail now)
+        struct Progs { KsfProg ksf; FilterProg flt; KmDevMap map; };
+        std::vector<Progs> progs(1);
+        memset((void*)progs.data(), 0, sizeof(Progs));
+        std::vector<GrpProg> probe(1);
+        std::string err;
+        rb = keyset_from_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, probe_keys, Q->hfields.data(),
+                               (int32_t)Q->hfields.size(), Q->walk, source_keys, probe.data(), &progs[0].ksf, err);
+        if (rb != CBX_OK) return fail(rb, err);
+        if (source_filter) {
+            rb = filter_build(Q->hfields.data(), (int32_t)Q->hfields.size(), Q->walk, source_filter, &progs[0].flt, err);
+            if (rb != CBX_OK) return fail(rb, err);
+        }
+        const size_t o_hdr = (sizeof(Progs) + 63) & ~(size_t)63;
+        AsyncBlock ws(st);
+        HIP_CHECK(hipMallocAsync(&ws.p, o_hdr + 8 * KM_WORDS, st));
+        uint8_t* b8 = (uint8_t*)ws.p;
+        KmDevMap& dm = progs[0].map;
+        dm.t = S->t;
+        dm.grp = (const CBX_CONST GrpProg*)(b8 + offsetof(Progs, ksf) + offsetof(KsfProg, src));
+        dm.first_row = M->first_row;
+        dm.n_rows = M->n_rows;
+        HIP_CHECK(hipMemcpyAsync(b8, progs.data(), sizeof(Progs), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(b8 + o_hdr, 0, 8 * KM_WORDS, st));
+        const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+        int64_t grid = std::min<int64_t>((n_tiles + kFltThreads / kWave - 1) / (kFltThreads / kWave), (int64_t)Q->num_cus * 8);
+        if (max_workgroups > 0) grid = std::min<int64_t>(grid, max_workgroups);
+        KmFillArgs g{};
+        FilterArgs& a = g.a;
+        a.data = d_data; a.n_bytes = n_bytes;
+        a.rec_off = in ? in->rec_off : d_rec_off;
+        a.rec_len = in ? in->rec_len : d_rec_len;
+        a.rec_seg = in ? in->segment : nullptr;
+        a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+        a.prog = source_filter ? (const CBX_CONST FilterProg*)(b8 + offsetof(Progs, flt)) : nullptr;
+        a.segmap = Q->opts.has_segments ? (const CBX_CONST cbx_segment_map*)Q->d_segmap : nullptr;
+        a.fields = (const CBX_CONST Field*)Q->d_fields;
+        a.lut = Q->d_lut;
+        g.map = (const CBX_CONST KmDevMap*)(b8 + offsetof(Progs, map));
+        g.has_filter = source_filter ? 1 : 0;
+        struct PassEvents {   // the events go back to the plan's pool on every exit path
+            cbx_plan* plan;
+            hipEvent_t e[2] = {nullptr, nullptr};
+            ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+        } pe{Q};
+        if (Q->profiling) {
+            for (int k = 0; k < 2; k++) if (!(pe.e[k] = take_event(Q))) return fail(CBX_E_HIP, "hipEventCreate failed");
+            HIP_CHECK(hipEventRecord(pe.e[0], st));
+        }
+        uint64_t* d_hdr = (uint64_t*)(b8 + o_hdr);
+        hipLaunchKernelGGL(keymap_init_kernel, dim3(blocks_for(nv, 256)), dim3(256), 0, st, M->first_row, M->n_rows, nv);
+        hipLaunchKernelGGL(keymap_fill_kernel, dim3((unsigned)grid), dim3(kFltThreads), 0, st, g);
+        hipLaunchKernelGGL(keymap_stats_kernel, dim3(blocks_for(nv, 256)), dim3(256), 0, st, (const int64_t*)M->first_row,
+                           (const int64_t*)M->n_rows, nv, d_hdr);
+        if (Q->profiling) HIP_CHECK(hipEventRecord(pe.e[1], st));
+        HIP_CHECK(hipGetLastError());
+        uint64_t hdr[KM_WORDS] = {};
+        HIP_CHECK(hipMemcpyAsync(hdr, d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));   // the two numbers
+        if (Q->profiling) HIP_CHECK(hipEventElapsedTime(&M->info.fill_ms, pe.e[0], pe.e[1]));
+        if (hdr[KM_UNFILLED] != 0)
+            return fail(CBX_E_STATE, "cbx_key_map_create_from_records: " + std::to_string(hdr[KM_UNFILLED]) +
+                                         " members were reached by no source row (internal error)");
+        M->info.n_duplicate_keys = (int64_t)hdr[KM_DUPLICATES];
+        M->info.max_rows_per_key = (int64_t)hdr[KM_MAX_ROWS];
+    }
+    if (info) *info = M->info;
+    guard.m = nullptr;
+    *out = M;
+    return CBX_OK;
+}
+
+// The join stage: keyed test with the map probe -> scan of the tile counts -> emit (the filter stage's own) and the
+// compaction of the match arrays.
+extern "C" int cbx_join_records(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                                const cbx_key_set* const* sets, const int32_t* negate, int32_t n_sets, const cbx_key_map* map,
+                                int32_t join_type, cbx_selection* out, int64_t* n_selected, int64_t* d_match,
+                                int64_t* d_match_rows, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !out || !n_selected || n_rec < 0 || n_bytes < 0 || start_offset < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: invalid arguments");
+    *n_selected = 0;
+    P->join_ms[0] = P->join_ms[1] = P->join_ms[2] = 0.f;
+    std::string err;
+    const int rc = km_join_check(map != nullptr, map && map->plan == P, join_type, d_match != nullptr, n_sets, sets != nullptr, err);
+    if (rc != CBX_OK) return fail(rc, err);
+    for (int s = 0; s < n_sets; s++) {
+        const std::string at = "cbx_join_records: set " + std::to_string(s) + ": ";
+        if (!sets[s]) return fail(CBX_E_ARGUMENT, at + "null");
+        if (sets[s]->plan != P) return fail(CBX_E_ARGUMENT, at + "built on another plan");
+        if (negate && negate[s] != 0 && sets[s]->t.n_keys != 1)
+            return fail(CBX_E_ARGUMENT, at + "only a single-column set may be negated");
+    }
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: exactly one source (selection, framed records, record stride)");
+    const int L = P->opts.has_segments ? P->opts.segments.n_levels : 0;
+    if (!in && L > 0)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: a plan with Seg_Id levels filters a selection (cbx_select_records)");
+    struct Progs { FilterProg flt; KsDevSet sets[CBX_GROUP_MAX_KEYS]; KmDevMap map; };
+    std::vector<Progs> prog(1);
+    memset((void*)prog.data(), 0, sizeof(Progs));
+    if (filter) {
+        const int rb = filter_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, filter, &prog[0].flt, err);
+        if (rb != CBX_OK) return fail(rb, err);
+    }
+    for (int s = 0; s < n_sets; s++) {
+        KsDevSet& d = prog[0].sets[s];
+        d.t = sets[s]->t;
+        d.grp = (const CBX_CONST GrpProg*)sets[s]->d_prog;
+        d.negate = negate && negate[s] != 0 ? 1 : 0;
+    }
+    prog[0].map.t = map->set->t;
+    prog[0].map.grp = (const CBX_CONST GrpProg*)map->set->d_prog;
+    prog[0].map.first_row = map->first_row;   // (nullptr for an empty map: no probe ever hits)
+    prog[0].map.n_rows = map->n_rows;
+    if (in) out->file_id = in->file_id;   // (an empty selection carries the batch's File_Id too)
+    if (n_rec == 0) return CBX_OK;
+    if (!d_data || !out->rec_off || !out->rec_len || !out->record_id || !out->segment ||
+        (in && (!in->rec_off || !in->rec_len || !in->record_id || !in->segment)) ||
+        (in && L > 0 && (!in->seg_state || !out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: selection arrays required");
+    if (in && (in->rec_off == out->rec_off || in->rec_len == out->rec_len || in->record_id == out->record_id ||
+               in->segment == out->segment || (L > 0 && in->seg_state == out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: out must not share arrays with in");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: n_rec records of rec_stride bytes exceed n_bytes");
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    const int64_t nb = scan_sums_len(n_tiles + 1);
+    // block: programs | keep words (n_tiles) | base (n_tiles + 1) | sums (nb) | match (n_rec) | rows (n_rec, when asked) |
+    // counts (n_tiles + 1) | segments (n_rec)
+    const size_t o_keep = (sizeof(Progs) + 15) & ~(size_t)15;
+    const size_t o_base = o_keep + sizeof(uint64_t) * n_tiles;
+    const size_t o_sums = o_base + sizeof(int64_t) * (n_tiles + 1);
+    const size_t o_match = o_sums + sizeof(int64_t) * nb;
+    const size_t o_rows = o_match + sizeof(int64_t) * (size_t)n_rec;
+    const size_t o_cnt = o_rows + (d_match_rows ? sizeof(int64_t) * (size_t)n_rec : 0);
+    AsyncBlock blk(st);
+    const size_t o_seg = o_cnt + sizeof(uint32_t) * (n_tiles + 2);
+    const bool map_seg = !in && P->opts.has_segments;   // the active segment comes from the plan's segment map
+    HIP_CHECK(hipMallocAsync(&blk.p, o_seg + (map_seg ? sizeof(int16_t) * (size_t)n_rec : 0) + 16, st));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    int64_t* base = (int64_t*)(b8 + o_base);
+    int64_t* sums = (int64_t*)(b8 + o_sums);
+    uint32_t* counts = (uint32_t*)(b8 + o_cnt);
+    HIP_CHECK(hipMemcpyAsync(b8, prog.data(), sizeof(Progs), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(counts + n_tiles, 0, sizeof(uint32_t), st));
+    KsArgs g{};
+    FilterArgs& a = g.a;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = (const CBX_CONST FilterProg*)b8;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    a.keep = (uint64_t*)(b8 + o_keep);
+    a.counts = counts;
+    a.seg_out = map_seg ? (int16_t*)(b8 + o_seg) : nullptr;
+    g.has_filter = filter ? 1 : 0;
+    g.n_sets = n_sets;
+    g.sets = (const CBX_CONST KsDevSet*)(b8 + offsetof(Progs, sets));
+    KmJoinArgs jn{};
+    jn.map = (const CBX_CONST KmDevMap*)(b8 + offsetof(Progs, map));
+    jn.match_tmp = (int64_t*)(b8 + o_match);
+    jn.rows_tmp = d_match_rows ? (int64_t*)(b8 + o_rows) : nullptr;
+    jn.join_type = join_type;
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    hipEvent_t* ev = pe.e;
+    if (P->profiling) {
+        for (int k = 0; k < 4; k++) if (!(ev[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    const unsigned grid = blocks_for(n_tiles, kFltThreads / kWave);
+    hipLaunchKernelGGL(keymap_test_kernel, dim3(grid), dim3(kFltThreads), 0, st, g, jn);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    device_scan(counts, n_tiles + 1, base, sums, st);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+    cbx_selection none{};
+    hipLaunchKernelGGL(filter_emit_kernel, dim3(grid), dim3(kFltThreads), 0, st, a, (const int64_t*)base, in ? *in : none,
+                       in ? 1 : 0, L > 0 ? 1 + L : 0, first_record_id, *out);
+    hipLaunchKernelGGL(keymap_emit_kernel, dim3(grid), dim3(kFltThreads), 0, st, (const uint64_t*)a.keep, (const int64_t*)base,
+                       n_tiles, (const int64_t*)jn.match_tmp, (const int64_t*)jn.rows_tmp, d_match, d_match_rows);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[3], st));
+    HIP_CHECK(hipGetLastError());
+    int64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, base + n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (P->profiling)
+        for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&P->join_ms[k], ev[k], ev[k + 1]));
+    *n_selected = total;
+    return CBX_OK;
+}
+
+extern "C" int cbx_join_pass_times(cbx_plan* P, float* test_ms, float* scan_ms, float* emit_ms) {
+    if (!P) return fail(CBX_E_ARGUMENT, "null plan");
+    if (test_ms) *test_ms = P->join_ms[0];
+    if (scan_ms) *scan_ms = P->join_ms[1];
+    if (emit_ms) *emit_ms = P->join_ms[2];
+    return CBX_OK;
+}
+
+// Rows of a record source by ordinal (ordinals_gather_kernel): one launch, no wait.
+extern "C" int cbx_select_ordinals(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                   const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                   int32_t start_offset, int64_t first_record_id, const int64_t* d_ordinals, int64_t n,
+                                   cbx_selection* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !out || n_rec < 0 || n_bytes < 0 || start_offset < 0 || n < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_select_ordinals: invalid arguments");
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_select_ordinals: exactly one source (selection, framed records, record stride)");
+    const int L = P->opts.has_segments ? P->opts.segments.n_levels : 0;
+    if (!in && L > 0)
+        return fail(CBX_E_ARGUMENT, "cbx_select_ordinals: a plan with Seg_Id levels takes a selection (cbx_select_records)");
+    if (in) out->file_id = in->file_id;
+    if (n == 0) return CBX_OK;
+    if (!d_ordinals || !out->rec_off || !out->rec_len || !out->record_id || !out->segment ||
+        (n_rec > 0 && !d_data) || (in && n_rec > 0 && (!in->rec_off || !in->rec_len || !in->record_id || !in->segment)) ||
+        (in && L > 0 && ((n_rec > 0 && !in->seg_state) || !out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_select_ordinals: ordinals and selection arrays required");
+    if (in && (in->rec_off == out->rec_off || in->rec_len == out->rec_len || in->record_id == out->record_id ||
+               in->segment == out->segment || (L > 0 && in->seg_state == out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_select_ordinals: out must not share arrays with in");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_select_ordinals: n_rec records of rec_stride bytes exceed n_bytes");
+    FilterArgs a{};
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = 0; a.stride = rec_stride; a.start_off = start_offset;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    cbx_selection none{};
+    hipLaunchKernelGGL(ordinals_gather_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, a, d_ordinals, n, in ? *in : none,
+                       in ? 1 : 0, L > 0 ? 1 + L : 0, first_record_id, *out);
+    HIP_CHECK(hipGetLastError());
     return CBX_OK;
 }
 

@@ -228,3 +228,122 @@ class KeySet:
 
     def __repr__(self) -> str:
         return f"KeySet({self.names}, n_values={self.n_values}, dropped={self.dropped}, closed={self.closed})"
+
+
+class DuplicateKeys(Exception):
+    """A lookup join over a key map whose dimension has duplicate keys: it would return the first matching dimension
+    row only (`duplicates="first"` asks for exactly that)."""
+
+    def __init__(self, n_duplicate_keys: int, max_rows_per_key: int):
+        super().__init__(f"{n_duplicate_keys} dimension keys have more than one row (up to {max_rows_per_key} rows per key): "
+                         "a lookup join returns the first one; pass duplicates='first' to accept that")
+        self.n_duplicate_keys = n_duplicate_keys
+        self.max_rows_per_key = max_rows_per_key
+
+
+def check_join(plan, key_map, how: str, duplicates: str) -> int:
+    """The join type (`native.JOIN_INNER` / `JOIN_LEFT`) of a join of `plan`'s rows against `key_map`, after every
+    refusal that needs no device: an unknown `how` or `duplicates`, a closed map, a map built for another reader's
+    plan, and -- with duplicates="error" -- `DuplicateKeys` when the dimension has a key on more than one row."""
+    if how not in ("inner", "left"):
+        raise ValueError(f"join: how={how!r} is neither 'inner' nor 'left' (a lookup join has no right or full form)")
+    if duplicates not in ("error", "first"):
+        raise ValueError(f"join: duplicates={duplicates!r} is neither 'error' nor 'first'")
+    if key_map.closed:
+        raise ValueError("the key map is closed")
+    if key_map.plan is not plan:
+        raise N.CbxError(N.CBX_E_ARGUMENT, "join: the key map was built for another reader's plan")
+    if duplicates == "error" and key_map.n_duplicate_keys > 0:
+        raise DuplicateKeys(key_map.n_duplicate_keys, key_map.max_rows_per_key)
+    return N.JOIN_INNER if how == "inner" else N.JOIN_LEFT
+
+
+class _KeySetView(KeySet):
+    """The member set of a key map: owned by the map, so closing the view frees nothing."""
+
+    def close(self) -> None:
+        self.handle = None
+
+
+class KeyMap:
+    """A device key map (`cbx_key_map_create_from_records`): the key set of `KeySet.from_records` whose members also
+    carry the ordinal of the first source (dimension) row with that key and the number of such rows -- what
+    `reader.join` probes.  Owns the library handle: `close()` (or the context manager) frees the device memory,
+    `key_set` included.
+
+    The map keeps a reference to the source reader, the source's device bytes and the record source its ordinals
+    index (`source`: n_rec / sel / rec_off / rec_len / stride), so `JoinResult.dimension()` can decode the matching
+    rows: THE SOURCE BYTES STAY RESIDENT ON THE DEVICE AS LONG AS THE MAP.  When the source filter held key sets of
+    its own, the keyed filter ran first and the ordinals index that intermediate selection (which the map keeps too),
+    not the file's records."""
+
+    def __init__(self):
+        raise TypeError("use KeyMap.from_records (reader.key_map_of / key_map_of_device)")
+
+    @classmethod
+    def from_records(cls, probe_plan, probe_handle, names: Sequence[str], source_plan, source_handle,
+                     source_names: Sequence[str], d_data_ptr: int, n_bytes: int, n_rec: int, *, sel_struct=None,
+                     rec_off_ptr=None, rec_len_ptr=None, stride: int = 0, start_offset: int = 0, filter_table=None,
+                     max_values: int = 65536, max_workgroups: int = 0, stream=None) -> "KeyMap":
+        """The arguments, refusals and counts of `KeySet.from_records`."""
+        ptable, stable = compile_key_pairs(probe_plan, names, source_plan, source_names)
+        info = N.CbxKeymapInfo()
+        h = ctypes.c_void_p()
+        rc = N.load().cbx_key_map_create_from_records(
+            probe_handle, ctypes.byref(ptable), source_handle, ctypes.byref(stable), d_data_ptr, n_bytes,
+            ctypes.byref(sel_struct) if sel_struct is not None else None, rec_off_ptr, rec_len_ptr, n_rec, stride,
+            start_offset, ctypes.byref(filter_table) if filter_table is not None else None, int(max_values),
+            max_workgroups, ctypes.c_void_p(stream.cuda_stream if stream is not None else 0), ctypes.byref(h),
+            ctypes.byref(info))
+        if rc == N.CBX_E_CAPACITY and info.overflow:
+            raise A.GroupOverflow(int(max_values))
+        N.check(rc)
+        self = cls.__new__(cls)
+        self.plan = probe_plan
+        self.names = list(names)
+        self.source_names = list(source_names)
+        self.source_info = info
+        self.dropped = info.n_dropped
+        self.has_null = info.n_null_rows > 0
+        self.n_values = info.n_source_keys - info.n_dropped
+        self.n_duplicate_keys = info.n_duplicate_keys
+        self.max_rows_per_key = info.max_rows_per_key
+        self.handle = h
+        self.source_reader = None   # set by the reader: what dimension() decodes with
+        self.source_data = None
+        self.source_bytes = 0
+        self.source = None
+        ks = _KeySetView.__new__(_KeySetView)
+        ks.plan, ks.names = probe_plan, list(names)
+        ks.dropped, ks.has_null, ks.n_values = self.dropped, self.has_null, self.n_values
+        ks.source_info = info
+        ks.handle = ctypes.c_void_p(N.load().cbx_key_map_set(h))
+        self.key_set = ks
+        return self
+
+    @property
+    def closed(self) -> bool:
+        return self.handle is None
+
+    def close(self) -> None:
+        if self.handle is not None:
+            self.key_set.close()
+            N.load().cbx_key_map_destroy(self.handle)
+            self.handle = None
+            self.source_reader = self.source_data = self.source = None
+
+    def __enter__(self) -> "KeyMap":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (interpreter shutdown)
+            pass
+
+    def __repr__(self) -> str:
+        return (f"KeyMap({self.source_names} -> {self.names}, n_values={self.n_values}, "
+                f"n_duplicate_keys={self.n_duplicate_keys}, closed={self.closed})")

@@ -50,7 +50,9 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_top_n_records", "cbx_top_n_info", "cbx_top_n_pass_times",
                     "cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy", "cbx_filter_records_keyed",
                     "cbx_key_set_create_from_records",
-                    "cbx_filter_max_op")
+                    "cbx_filter_max_op",
+                    "cbx_key_map_create_from_records", "cbx_key_map_info", "cbx_key_map_destroy", "cbx_key_map_set",
+                    "cbx_join_records", "cbx_select_ordinals", "cbx_join_pass_times")
 # grouped aggregates were an additive extension of ABI 24: the symbols are required
 GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
 # Top-N / LIMIT pushdown was an additive extension of ABI 25: the symbols are required
@@ -61,6 +63,9 @@ KEYSET_SYMBOLS = ("cbx_key_set_create", "cbx_key_set_info", "cbx_key_set_destroy
 KEYSET_FROM_SYMBOLS = ("cbx_key_set_create_from_records",)
 # suffix / substring filter ops were an additive extension of ABI 25: the symbol is required
 FILTER_STRING_SYMBOLS = ("cbx_filter_max_op",)
+# lookup joins (key maps, the join stage, rows by ordinal) were an additive extension of ABI 25: the symbols are required
+KEYMAP_SYMBOLS = ("cbx_key_map_create_from_records", "cbx_key_map_info", "cbx_key_map_destroy", "cbx_key_map_set",
+                  "cbx_join_records", "cbx_select_ordinals", "cbx_join_pass_times")
 ABI_VERSION = 25
 
 
@@ -268,6 +273,15 @@ class CbxKeysetSourceInfo(ctypes.Structure):
                 ("convert_ms", ctypes.c_float)]
 
 
+class CbxKeymapInfo(ctypes.Structure):
+    """cbx_key_map_info: cbx_keyset_source_info's fields, then what the fill pass found."""
+    _fields_ = CbxKeysetSourceInfo._fields_ + [("n_duplicate_keys", ctypes.c_int64), ("max_rows_per_key", ctypes.c_int64),
+                                               ("fill_ms", ctypes.c_float), ("reserved2", ctypes.c_int32)]
+
+
+JOIN_INNER, JOIN_LEFT = 0, 1
+
+
 W_GROUP, W_PRIM = 0, 1
 W_REDEFINED, W_REDEFINES = 0x1, 0x2
 
@@ -419,7 +433,15 @@ def load():
                      ("cbx_key_set_destroy", [P]),
                      ("cbx_filter_records_keyed", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, i32, P, P, P]),
                      ("cbx_key_set_create_from_records", [P, P, P, P, P, i64, P, P, P, i64, i32, i32, P, i64, i32, P,
-                                                          ctypes.POINTER(P), P])):
+                                                          ctypes.POINTER(P), P]),
+                     ("cbx_key_map_create_from_records", [P, P, P, P, P, i64, P, P, P, i64, i32, i32, P, i64, i32, P,
+                                                          ctypes.POINTER(P), P]),
+                     ("cbx_key_map_info", [P, P]),
+                     ("cbx_key_map_destroy", [P]),
+                     ("cbx_key_map_set", [P]),
+                     ("cbx_join_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, i32, P, i32, P, P, P, P, P]),
+                     ("cbx_select_ordinals", [P, P, i64, P, P, P, i64, i32, i32, i64, P, i64, P, P]),
+                     ("cbx_join_pass_times", [P, P, P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):
@@ -441,8 +463,14 @@ def load():
     missing = [n for n in FILTER_STRING_SYMBOLS if not hasattr(L, n)]
     if missing and not os.environ.get("CBX_LIB_VARIANT"):
         raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (suffix / substring filter ops); rebuild it")
+    missing = [n for n in KEYMAP_SYMBOLS if not hasattr(L, n)]
+    if missing and not os.environ.get("CBX_LIB_VARIANT"):
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (lookup joins); rebuild it")
     if hasattr(L, "cbx_key_set_destroy"):
         L.cbx_key_set_destroy.restype = None
+    if hasattr(L, "cbx_key_map_destroy"):
+        L.cbx_key_map_destroy.restype = None
+        L.cbx_key_map_set.restype = P
     if hasattr(L, "cbx_filter_max_op"):
         L.cbx_filter_max_op.argtypes = []
         L.cbx_filter_max_op.restype = i32

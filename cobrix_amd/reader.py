@@ -25,7 +25,7 @@ from .aggregate import (AggregateResult, GroupedAggregateResult, GroupOverflow, 
                         compile_group_by)
 from .aggregate import Unhandled as AggregateUnhandled
 from .filter import compile_filters_with_sets
-from .keyset import KeySet
+from .keyset import KeyMap, KeySet, check_join
 from .plan import DecodePlan, NativePlan, NeedsWalk, build_plan
 from .topn import compile_order
 from .schema import ST_DECIMAL, spark_schema
@@ -1104,6 +1104,90 @@ class _BaseReader:
             start_offset=self.params.start_offset, filter_table=flt, max_values=max_values, max_workgroups=max_workgroups,
             stream=st)
 
+    def _key_map_from(self, source_names, probe, names, filters, max_values: int, d_data, n_bytes: int, n_rec: int, st, *,
+                      sel=None, rec_off=None, rec_len=None, stride: int = 0, file_id: int = 0, first_record_id: int = 0,
+                      max_workgroups: int = 0) -> KeyMap:
+        """cbx_key_map_create_from_records with this reader as the source (the dimension): `_key_set_from`'s set whose
+        members carry the ordinal of their first source row.  All or nothing in the same way.  The map keeps this
+        reader, the device bytes and the record source its ordinals index -- the keyed filter's selection when
+        `filters` hold key sets of this reader."""
+        source_names = list(source_names)
+        names = list(names) if names is not None else source_names
+        flt, src = self._pushed_filter(filters, d_data, n_bytes, n_rec, st, sel=sel, rec_off=rec_off, rec_len=rec_len,
+                                       stride=stride, first_record_id=first_record_id, file_id=file_id)
+        n_rec, sel, rec_off, rec_len, stride = src["n_rec"], src["sel"], src["rec_off"], src["rec_len"], src["stride"]
+        km = KeyMap.from_records(
+            probe.plan, probe.native.handle, names, self.plan, self.native.handle, source_names, d_data.data_ptr(), n_bytes,
+            n_rec, sel_struct=sel["struct"] if sel is not None else None,
+            rec_off_ptr=rec_off.data_ptr() if rec_off is not None else None,
+            rec_len_ptr=rec_len.data_ptr() if rec_len is not None else None, stride=stride,
+            start_offset=self.params.start_offset, filter_table=flt, max_values=max_values, max_workgroups=max_workgroups,
+            stream=st)
+        km.source_reader, km.source_data, km.source_bytes = self, d_data, n_bytes
+        km.source = dict(src, first_record_id=first_record_id, file_id=file_id)
+        return km
+
+    def _select_ordinals(self, ordinals, d_data, n_bytes: int, st, *, n_rec: int, sel=None, rec_off=None, rec_len=None,
+                         stride: int = 0, first_record_id: int = 0, file_id: int = 0) -> Dict[str, Any]:
+        """cbx_select_ordinals: the rows `ordinals` (an int64 device tensor; any order, repeats allowed) of one record
+        source as a selection for cbx_decode_selected.  An ordinal outside [0, n_rec) gives a zero-length record."""
+        n = int(ordinals.numel())
+        out, cs = self._empty_selection(n, d_data.device)
+        cs.file_id = sel["struct"].file_id if sel is not None else file_id
+        N.check(N.load().cbx_select_ordinals(
+            self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+            rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+            n_rec, stride, self.params.start_offset, first_record_id, ordinals.data_ptr() if n else None, n,
+            ctypes.byref(cs), ctypes.c_void_p(st.cuda_stream)))
+        out["n"] = n
+        out["struct"] = cs
+        out["source"] = (sel, ordinals)   # (the arrays the launch reads stay alive with the result)
+        out["unhandled"] = []
+        return out
+
+    def _join_records(self, key_map: KeyMap, how: str, filters, duplicates: str, d_data, n_bytes: int, n_rec: int, st, *,
+                      sel=None, rec_off=None, rec_len=None, stride: int = 0, first_record_id: int = 0,
+                      file_id: int = 0, decode: bool = True) -> "JoinResult":
+        """cbx_join_records over one source through the full plan, then the decode of the kept rows.  All or nothing:
+        `keyset.DuplicateKeys` (duplicates="error") and a filter that is not pushed down raise before any launch.
+        decode=False: `batch` is None (timing tools)."""
+        join_type = check_join(self.plan, key_map, how, duplicates)
+        table, sets, negate = None, [], []
+        if filters:
+            table, sets, negate, unhandled = compile_filters_with_sets(self.plan, filters)
+            if unhandled:
+                raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        torch = _torch()
+        out, cs = self._empty_selection(n_rec, d_data.device)
+        cs.file_id = sel["struct"].file_id if sel is not None else file_id
+        match = torch.empty(max(1, n_rec), dtype=torch.int64, device=d_data.device)
+        match_rows = torch.empty(max(1, n_rec), dtype=torch.int64, device=d_data.device)
+        ns = ctypes.c_int64(0)
+        handles = (ctypes.c_void_p * max(1, len(sets)))(*[s.handle for s in sets])
+        neg = (ctypes.c_int32 * max(1, len(sets)))(*negate)
+        N.check(N.load().cbx_join_records(
+            self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+            rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+            n_rec, stride, self.params.start_offset, first_record_id, ctypes.byref(table) if table is not None else None,
+            ctypes.addressof(handles) if sets else None, ctypes.addressof(neg) if sets else None, len(sets), key_map.handle,
+            join_type, ctypes.byref(cs), ctypes.byref(ns), match.data_ptr(), match_rows.data_ptr(),
+            ctypes.c_void_p(st.cuda_stream)))
+        out["n"] = ns.value
+        out["struct"] = cs
+        out["source"] = sel
+        out["unhandled"] = []
+        batch = None
+        if decode:
+            batch = self._decode_rows(d_data, n_bytes, out, st)
+            batch.unhandled_filters = []
+        return JoinResult(key_map, how, batch, out, match[:ns.value], match_rows[:ns.value], st)
+
+    def join_pass_times(self) -> Tuple[float, float, float]:
+        """(test, scan, emit) ms of the last join call (cbx_plan_set_profiling on; zeros otherwise)."""
+        t, s_, e = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
+        N.check(N.load().cbx_join_pass_times(self.native.handle, ctypes.byref(t), ctypes.byref(s_), ctypes.byref(e)))
+        return t.value, s_.value, e.value
+
     def group_pass_times(self) -> Tuple[float, float, float]:
         """(init, accumulate, emit) ms of the last grouped aggregate call (cbx_plan_set_profiling on; zeros otherwise)."""
         i, a, e = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
@@ -1172,6 +1256,56 @@ class _BaseReader:
         if self.out_native is not None and self.out_native is not self.native:
             self.out_native.close()
         self.native.close()
+
+
+class JoinResult:
+    """What `join` / `join_device` return: a LOOKUP join of a fact scan against a key map's dimension.
+    `batch`: the kept fact rows, decoded (in source order); `selection`: their selection; `match`: int64 device
+    tensor, per kept row the ordinal of the first dimension row with its key or -1; `matched`: match >= 0;
+    `match_rows`: how many dimension rows had that key (0 where unmatched).  With `n_duplicate_keys == 0` on the map
+    this is SQL's inner / left join; with duplicates the first dimension row stands for all of them."""
+
+    def __init__(self, key_map: KeyMap, how: str, batch: DecodedBatch, selection: Dict[str, Any], match, match_rows, stream):
+        self.key_map, self.how, self.batch, self.selection = key_map, how, batch, selection
+        self.match, self.match_rows = match, match_rows
+        self.matched = match >= 0
+        self._stream = stream
+
+    def _dimension_of(self, ordinals) -> DecodedBatch:
+        km = self.key_map
+        if km.closed or km.source_reader is None:
+            raise ValueError("the key map is closed: its source is gone")
+        rd, src = km.source_reader, km.source
+        sel = rd._select_ordinals(ordinals.contiguous(), km.source_data, km.source_bytes, self._stream, n_rec=src["n_rec"],
+                                  sel=src["sel"], rec_off=src["rec_off"], rec_len=src["rec_len"], stride=src["stride"],
+                                  first_record_id=src["first_record_id"], file_id=src["file_id"])
+        return rd._decode_rows(km.source_data, km.source_bytes, sel, self._stream)
+
+    def dimension(self) -> DecodedBatch:
+        """The dimension rows of the matched fact rows, in their order (match[matched] -> cbx_select_ordinals on the
+        source reader -> its selected decode)."""
+        return self._dimension_of(self.match[self.matched])
+
+    def rows(self, prefix: str = "") -> List[dict]:
+        """The fact row dicts with the dimension's fields beside them: None for every dimension field of an unmatched
+        LEFT row.  `prefix` is put in front of every dimension field name; a name that then still collides with a
+        fact field raises ValueError."""
+        fact = self.batch.to_rows()
+        if not fact:
+            return []
+        # (an unmatched row's ordinal -1 lies outside the source: a zero-length record, whose row has the field names)
+        dim = self._dimension_of(self.match).to_rows()
+        hit = self.matched.cpu().tolist()
+        out = []
+        for f, d, h in zip(fact, dim, hit):
+            row = dict(f)
+            for k, v in d.items():
+                name = prefix + k
+                if name in f:
+                    raise ValueError(f"dimension field {name!r} collides with a fact field: pass prefix=")
+                row[name] = v if h else None
+            out.append(row)
+        return out
 
 
 class FixedLenNestedReader(_BaseReader):
@@ -1369,6 +1503,49 @@ class FixedLenNestedReader(_BaseReader):
         self.check_binary_data_validity(len(data))
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
         return self.key_set_of_device(t, len(data), source_names, probe, names, filters, max_values)
+
+    def _decode_rows(self, d_data, n_bytes: int, sel: Dict[str, Any], st) -> DecodedBatch:
+        return self._decode_selection(d_data, n_bytes, sel, False, st)
+
+    def key_map_of_device(self, d_data, n_bytes: int, source_names, probe, names=None, filters=None, max_values: int = 65536,
+                          stream=None, max_workgroups: int = 0) -> KeyMap:
+        """A key map of reader `probe` over its columns `names` (default: source_names) from this (dimension) reader's
+        rows that `filters` keep: `key_set_of_device`'s set -- its pairing rules, drops, refusals and overflow --
+        whose members carry the ordinal of the first row with that key and the number of such rows, for `probe.join`.
+        `d_data` stays referenced by the map (see `keyset.KeyMap`)."""
+        torch = _torch()
+        stride = self.get_record_size()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        return self._key_map_from(source_names, probe, names, filters, max_values, d_data, n_bytes, n_bytes // stride, st,
+                                  stride=stride, max_workgroups=max_workgroups)
+
+    def key_map_of(self, data: bytes, source_names, probe, names=None, filters=None, max_values: int = 65536) -> KeyMap:
+        """`key_map_of_device` over host bytes, with the file-size checks of `decode`."""
+        torch = _torch()
+        self.check_binary_data_validity(len(data))
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        return self.key_map_of_device(t, len(data), source_names, probe, names, filters, max_values)
+
+    def join_device(self, d_data, n_bytes: int, key_map: KeyMap, how: str = "inner", filters=None, duplicates: str = "error",
+                    first_record_id: int = 0, stream=None) -> JoinResult:
+        """A broadcast lookup join of this (fact) reader's rows against a key map built for it: the rows `filters`
+        keep whose key is a member (how="inner") or all of them (how="left"), each with the ordinal of its dimension
+        row (`JoinResult`).  duplicates="error" raises `keyset.DuplicateKeys` when the dimension has a key on more
+        than one row; duplicates="first" takes the first such row.  A filter that is not pushed down raises
+        `aggregate.Unhandled`, as in the other all-or-nothing stages."""
+        torch = _torch()
+        stride = self.get_record_size()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        return self._join_records(key_map, how, filters, duplicates, d_data, n_bytes, n_bytes // stride, st, stride=stride,
+                                  first_record_id=first_record_id)
+
+    def join(self, data: bytes, key_map: KeyMap, how: str = "inner", filters=None, duplicates: str = "error",
+             first_record_id: int = 0) -> JoinResult:
+        """`join_device` over host bytes, with the file-size checks of `decode`."""
+        torch = _torch()
+        self.check_binary_data_validity(len(data))
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        return self.join_device(t, len(data), key_map, how, filters, duplicates, first_record_id)
 
     def top_n_device(self, d_data, n_bytes: int, orders, limit: int, filters=None, first_record_id: int = 0,
                      stream=None, max_workgroups: int = 0) -> DecodedBatch:
@@ -2225,6 +2402,69 @@ class VarLenNestedReader(_BaseReader):
             entries = self.generate_index(t, len(data), off, ln, file_id)
         sel = self.select(t, vb, off, ln, entries, file_id)
         return self.key_set_of_device(t, vb, sel, source_names, probe, names, filters, max_values, file_id)
+
+    def _decode_rows(self, d_data, n_bytes: int, sel: Dict[str, Any], st) -> DecodedBatch:
+        return self.decode_selected(d_data, n_bytes, sel, st)
+
+    def _whole_file_selection(self, data: bytes, file_id: int):
+        t = self._device_file(data)
+        off, ln, vb = self.frame_file(t, len(data))
+        entries = None
+        if self.index_generation_needed() and not self.params.is_text:
+            entries = self.generate_index(t, len(data), off, ln, file_id)
+        return t, vb, self.select(t, vb, off, ln, entries, file_id)
+
+    def key_map_of_device(self, d_data, n_bytes: int, sel_or_framing, source_names, probe, names=None, filters=None,
+                          max_values: int = 65536, file_id: int = 0, stream=None, max_workgroups: int = 0) -> KeyMap:
+        """A key map of reader `probe` from a selection or framed records of this (dimension) reader, as
+        `key_set_of_device`; see `FixedLenNestedReader.key_map_of_device`.  The ordinals index the selection or the
+        framed records handed in.  Hierarchical reads refuse."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "key maps of a hierarchical read: rows are trees of segments")
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if isinstance(sel_or_framing, dict):
+            return self._key_map_from(source_names, probe, names, filters, max_values, d_data, n_bytes, sel_or_framing["n"],
+                                      st, sel=sel_or_framing, file_id=file_id, max_workgroups=max_workgroups)
+        rec_off, rec_len = sel_or_framing
+        return self._key_map_from(source_names, probe, names, filters, max_values, d_data, n_bytes, int(rec_off.numel()), st,
+                                  rec_off=rec_off, rec_len=rec_len, file_id=file_id, max_workgroups=max_workgroups)
+
+    def key_map_of(self, data: bytes, source_names, probe, names=None, filters=None, max_values: int = 65536,
+                   file_id: int = 0) -> KeyMap:
+        """`key_map_of_device` over a whole file: the row set of `read` (framing, sparse index, selection with
+        segment_filter and file_end_offset, then the filters)."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "key maps of a hierarchical read: rows are trees of segments")
+        t, vb, sel = self._whole_file_selection(data, file_id)
+        return self.key_map_of_device(t, vb, sel, source_names, probe, names, filters, max_values, file_id)
+
+    def join_device(self, d_data, n_bytes: int, sel_or_framing, key_map: KeyMap, how: str = "inner", filters=None,
+                    duplicates: str = "error", first_record_id: int = 0, file_id: int = 0, stream=None) -> JoinResult:
+        """A broadcast lookup join of a selection or framed records of this (fact) reader against a key map built
+        for it; see `FixedLenNestedReader.join_device`.  A reader with segment id levels takes a selection only, as
+        `filter`; hierarchical reads refuse."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "joins on a hierarchical read: rows are trees of segments")
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if isinstance(sel_or_framing, dict):
+            return self._join_records(key_map, how, filters, duplicates, d_data, n_bytes, sel_or_framing["n"], st,
+                                      sel=sel_or_framing)
+        if self.plan.seg_id_columns:
+            raise N.CbxError(N.CBX_E_ARGUMENT, "join: a reader with segment id levels takes a selection "
+                                               "(the Seg_IdN state comes from select()); pass select()'s result")
+        rec_off, rec_len = sel_or_framing
+        return self._join_records(key_map, how, filters, duplicates, d_data, n_bytes, int(rec_off.numel()), st,
+                                  rec_off=rec_off, rec_len=rec_len, first_record_id=first_record_id, file_id=file_id)
+
+    def join(self, data: bytes, key_map: KeyMap, how: str = "inner", filters=None, duplicates: str = "error",
+             first_record_id: int = 0, file_id: int = 0) -> JoinResult:
+        """`join_device` over a whole file: of the rows `read(data, filters=filters)` would return."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "joins on a hierarchical read: rows are trees of segments")
+        t, vb, sel = self._whole_file_selection(data, file_id)
+        return self.join_device(t, vb, sel, key_map, how, filters, duplicates, first_record_id, file_id)
 
     def top_n_device(self, d_data, n_bytes: int, sel_or_framing, orders, limit: int, filters=None,
                      first_record_id: int = 0, file_id: int = 0, stream=None, max_workgroups: int = 0) -> DecodedBatch:

@@ -869,6 +869,101 @@ int cbx_key_set_create_from_records(cbx_plan* probe_plan, const cbx_group_by* pr
                                     const cbx_filter* source_filter, int64_t max_values, int32_t max_workgroups,
                                     void* stream, cbx_key_set** out, cbx_keyset_source_info* info /* may be NULL */);
 
+/* ---- lookup joins: key maps and the join stage: an additive extension of ABI 25 ----
+ *
+ * The question after the semi join: "and give me the dimension's columns beside each fact row".  A key map is a key
+ * set whose members remember the dimension row they came from; the join stage is the keyed filter stage that also
+ * emits, per kept fact row, the matching dimension row; cbx_select_ordinals turns those rows into a selection of the
+ * dimension file that cbx_decode_selected takes.  No structure and no entry point above changes, so CBX_ABI_VERSION
+ * stays 25; a caller checks for the six symbols below.
+ * Key map, over decoded values.  Let S be the set cbx_key_set_create_from_records builds from the same arguments: the
+ * accepted record sources, the pairing rules of the key columns, the scale rule, the drop rules, max_values, the
+ * overflow behaviour, the refusals and their messages are that call's, unchanged.  Number the records of the source's
+ * record source 0 .. n_rec - 1 (the position in the source handed to the call, not the position among the kept rows).
+ * For every member v of S, first_row[v] is the smallest ordinal among the source rows source_filter keeps whose key
+ * equals v, and n_rows[v] is the number of such rows.  n_duplicate_keys is the number of members with n_rows > 1,
+ * max_rows_per_key the largest n_rows (0 for an empty map).  None of this depends on timing, on max_workgroups or on
+ * which lane claimed a slot: first_row is a minimum, not the distinct pass's representative.
+ * Passes: those of cbx_key_set_create_from_records, then fill (one more pass over the source records: the source
+ * filter, then every kept record probes the finished set through the SOURCE plan's key program and, on a hit, does
+ * one 64-bit atomic min on first_row and one 64-bit atomic add on n_rows, relaxed, device scope) and stats (one lane
+ * per value).  Host waits: four -- the set's three and one after the stats pass for the two numbers.  An empty set
+ * launches neither pass and does not wait again.  The map holds the set's device memory and 16 bytes per value.
+ * Join.  K(r): the cbx_filter is true for r and every set's verdict is true for r, exactly as cbx_filter_records_keyed
+ * decides it (here n_sets may be 0 and filter NULL: then K is true).  m(r): first_row of the member equal to r's key
+ * over the map's probe columns, -1 when a key component is null or the key is no member.  CBX_JOIN_INNER keeps r when
+ * K(r) and m(r) >= 0; CBX_JOIN_LEFT keeps r when K(r).  `out` is the selection of the kept rows in source order --
+ * for INNER bit-identical to cbx_filter_records_keyed with the map's set added as one more IN set --, *n_selected
+ * their number, d_match[j] (device, capacity n_rec) m of the j-th kept row, d_match_rows[j] (device, capacity n_rec;
+ * may be NULL) n_rows of that member, 0 where m = -1.
+ * THIS IS A LOOKUP JOIN: it equals SQL's inner / left join exactly when n_duplicate_keys == 0.  With duplicate
+ * dimension keys it returns the first matching dimension row, and d_match_rows says how many there were.
+ * Passes: test (the keyed test pass, then the map probe for lanes still kept: one value-index lookup, one 8-byte
+ * load and one 8-byte store per kept row into a per-input-record array from the stream's pool), the filter stage's
+ * scan, emit (filter_emit_kernel unchanged, then the compaction of the match arrays with the same keep words).
+ * Host waits: one, as cbx_filter_records.  n_rec == 0 launches nothing. */
+#define CBX_JOIN_INNER 0
+#define CBX_JOIN_LEFT 1
+typedef struct cbx_key_map cbx_key_map;
+typedef struct cbx_keymap_info {
+    int64_t n_rows;        /* as cbx_keyset_source_info, field by field ... */
+    int64_t n_null_rows;
+    int64_t n_source_keys;
+    int64_t n_dropped;
+    int64_t source_capacity, workspace_bytes;
+    int32_t overflow;
+    int32_t reserved;
+    float distinct_ms, convert_ms;
+    int64_t n_duplicate_keys;   /* ... then: members with more than one source row */
+    int64_t max_rows_per_key;   /* the largest number of source rows of one member */
+    float fill_ms;              /* init + fill + stats, HIP events while cbx_plan_set_profiling(source_plan) is on */
+    int32_t reserved2;
+} cbx_keymap_info;
+
+/* The arguments of cbx_key_set_create_from_records.  On any error *out is NULL and no device memory is held. */
+int cbx_key_map_create_from_records(cbx_plan* probe_plan, const cbx_group_by* probe_keys, cbx_plan* source_plan,
+                                    const cbx_group_by* source_keys, const uint8_t* d_data, int64_t n_bytes,
+                                    const cbx_selection* in, const int64_t* d_rec_off, const int32_t* d_rec_len,
+                                    int64_t n_rec, int32_t rec_stride, int32_t start_offset,
+                                    const cbx_filter* source_filter, int64_t max_values, int32_t max_workgroups,
+                                    void* stream, cbx_key_map** out, cbx_keymap_info* info /* may be NULL */);
+
+/* What the build of the map found (host code only, no GPU work). */
+int cbx_key_map_info(const cbx_key_map* map, cbx_keymap_info* out);
+
+/* Frees the map, its set included; no call that probes either may still be running.  NULL is allowed. */
+void cbx_key_map_destroy(cbx_key_map* map);
+
+/* The member set S: owned by the map and valid until cbx_key_map_destroy.  It is a set of probe_plan like any other
+ * (cbx_key_set_info, cbx_filter_records_keyed), but it MUST NOT be passed to cbx_key_set_destroy.  NULL for NULL. */
+const cbx_key_set* cbx_key_map_set(const cbx_key_map* map);
+
+/* As cbx_filter_records_keyed with 0 to CBX_GROUP_MAX_KEYS sets (sets / negate may be NULL when n_sets == 0), one
+ * key map of `plan` and a join type.  CBX_E_ARGUMENT: a NULL map, a map built for another probe plan, a join_type
+ * other than the two, a NULL d_match, and whatever cbx_filter_records_keyed refuses. */
+int cbx_join_records(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                     const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                     int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                     const cbx_key_set* const* sets, const int32_t* negate, int32_t n_sets, const cbx_key_map* map,
+                     int32_t join_type, cbx_selection* out, int64_t* n_selected, int64_t* d_match,
+                     int64_t* d_match_rows /* may be NULL */, void* stream);
+
+/* Rows of a record source by ordinal (independent of maps): row j of `out` (capacity n) is exactly the row
+ * filter_emit_kernel writes for record d_ordinals[j] (device, n values) of the record source, which is given as to
+ * cbx_filter_records.  With an `in` selection its rec_off, rec_len, record_id, segment and seg_state are carried
+ * over; otherwise the row has the framed or fixed-length offset and length, first_record_id + ordinal, and the
+ * segment from the plan's segment map or -1.  Ordinals may repeat and come in any order.  An ordinal outside
+ * [0, n_rec) gives a zero-length record at offset 0 (record id -1, segment -1): the host cannot check this without a
+ * wait, so the call does not.  One launch, no host wait: `out` is complete when `stream` reaches this point. */
+int cbx_select_ordinals(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                        const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                        int32_t start_offset, int64_t first_record_id, const int64_t* d_ordinals, int64_t n,
+                        cbx_selection* out, void* stream);
+
+/* Durations in ms of the plan's last cbx_join_records call: test, scan, emit (both emit launches), measured with HIP
+ * events while cbx_plan_set_profiling is on. */
+int cbx_join_pass_times(cbx_plan* plan, float* test_ms, float* scan_ms, float* emit_ms);
+
 /* ---- the record walk with data-dependent offsets ----
  *
  * Layouts the static-offset tables above cannot express run through a per-record walk of the
