@@ -33,6 +33,7 @@
 #include "cbx_keyset.h"
 #include "cbx_keyset_from.h"
 #include "cbx_keymap.h"
+#include "cbx_keymap_rows.h"
 #include "cbx_gather.h"
 
 using namespace cbx;
@@ -178,6 +179,8 @@ struct cbx_plan {
     std::vector<CallEvents> ev_calls;    // recorded, not yet read
     float flt_ms[3] = {0.f, 0.f, 0.f};   // test / scan / emit of the last cbx_filter_records call (profiling)
     float join_ms[3] = {0.f, 0.f, 0.f};  // test / scan / emit of the last cbx_join_records call (profiling)
+    float fx_ms[3] = {0.f, 0.f, 0.f};    // test / scan / emit of the last cbx_join_records_expand call (profiling)
+    cbx_expand_info last_fx{};      // cbx_join_expand_info: how the last cbx_join_records_expand call ran
     float grp_ms[3] = {0.f, 0.f, 0.f};   // init / accumulate / emit of the last cbx_aggregate_grouped call (profiling)
     float agg_ms[2] = {0.f, 0.f};        // accumulate / combine of the last cbx_aggregate_records call (profiling)
     float topn_ms[3] = {0.f, 0.f, 0.f};  // key / select / emit of the last cbx_top_n_records call (profiling)
@@ -3219,11 +3222,20 @@ struct cbx_key_map {
     int64_t* first_row = nullptr;
     int64_t* n_rows = nullptr;
     cbx_keymap_info info{};
+    // what cbx_key_map_index_rows needs of the build, and what it adds (cbx_keymap_rows.h)
+    const cbx_plan* source_plan = nullptr;
+    int64_t source_n_rec = 0;
+    cbx_group_by probe_keys{};
+    void* row_mem = nullptr;          // row_start (n_values + 1) | rows (cap)
+    int64_t* row_start = nullptr;
+    int64_t* rows = nullptr;
+    cbx_keymap_rows_info rinfo{};
 };
 
 extern "C" void cbx_key_map_destroy(cbx_key_map* M) {
     if (!M) return;
     if (M->payload) (void)hipFree(M->payload);
+    if (M->row_mem) (void)hipFree(M->row_mem);
     cbx_key_set_destroy(M->set);
     delete M;
 }
@@ -3265,6 +3277,11 @@ extern "C" int cbx_key_map_create_from_records(cbx_plan* P, const cbx_group_by* 
     M->plan = P;
     M->set = S;
     M->info = mi;
+    M->source_plan = Q;
+    M->source_n_rec = n_rec;
+    M->probe_keys = *probe_keys;
+    M->rinfo.short_max = kRowsShortMax;
+    M->rinfo.lds_max = kRowsLdsMax;
     const int64_t nv = S->t.n_values;
     if (nv > 0 && n_rec > 0) {
         HIP_CHECK(hipMalloc(&M->payload, 16 * (size_t)nv));
@@ -3477,6 +3494,361 @@ extern "C" int cbx_join_pass_times(cbx_plan* P, float* test_ms, float* scan_ms, 
     if (test_ms) *test_ms = P->join_ms[0];
     if (scan_ms) *scan_ms = P->join_ms[1];
     if (emit_ms) *emit_ms = P->join_ms[2];
+    return CBX_OK;
+}
+
+// Fan-out joins (cbx_keymap_rows.h): per-key row lists on a map, and the join stage with one output row per match.
+namespace {
+// exclusive scan of n int64 values into out[0 .. n]; n_dev (device) overrides n for the kernels, the grid covers n
+void device_scan64(const int64_t* in, int64_t n, const int64_t* n_dev, int64_t* out, int64_t* sums, uint64_t* total_out,
+                   hipStream_t st) {
+    const int64_t nb = (n + 1 + kScan64Tile - 1) / kScan64Tile;
+    hipLaunchKernelGGL(scan64_reduce_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, st, in, n, n_dev, sums);
+    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(kScanBlock), 0, st, sums, nb);
+    hipLaunchKernelGGL(scan64_apply_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, st, in, n, n_dev, (const int64_t*)sums, out,
+                       total_out);
+}
+int64_t scan64_sums_len(int64_t n) { return (n + 1 + kScan64Tile - 1) / kScan64Tile; }
+}  // namespace
+
+extern "C" int cbx_key_map_rows_info(const cbx_key_map* M, cbx_keymap_rows_info* out) {
+    if (!M || !out) return fail(CBX_E_ARGUMENT, "cbx_key_map_rows_info: invalid arguments");
+    *out = M->rinfo;
+    return CBX_OK;
+}
+
+extern "C" int cbx_key_map_rows(const cbx_key_map* M, const int64_t** d_row_start, const int64_t** d_rows) {
+    if (!M || !d_row_start || !d_rows) return fail(CBX_E_ARGUMENT, "cbx_key_map_rows: invalid arguments");
+    *d_row_start = M->rinfo.has_rows ? M->row_start : nullptr;
+    *d_rows = M->rinfo.has_rows ? M->rows : nullptr;
+    return CBX_OK;
+}
+
+// scan -> scatter -> classify (+ the short sort) -> LDS sort -> global sort -> check, and one wait for the header.
+extern "C" int cbx_key_map_index_rows(cbx_key_map* M, cbx_plan* Q, const cbx_group_by* source_keys, const uint8_t* d_data,
+                                      int64_t n_bytes, const cbx_selection* in, const int64_t* d_rec_off,
+                                      const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride, int32_t start_offset,
+                                      const cbx_filter* source_filter, int32_t max_workgroups, void* stream,
+                                      cbx_keymap_rows_info* info) {
+    hipStream_t st = (hipStream_t)stream;
+    if (info) memset(info, 0, sizeof(*info));
+    std::string err;
+    int rb = km_rows_check(M != nullptr, M && Q && M->source_plan == Q, n_rec, M ? M->source_n_rec : 0, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    if (!source_keys || n_bytes < 0 || start_offset < 0 || max_workgroups < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_key_map_index_rows: invalid arguments");
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_key_map_index_rows: exactly one source (selection, framed records, record stride)");
+    if (M->rinfo.has_rows) { if (info) *info = M->rinfo; return CBX_OK; }
+    const int64_t nv = M->set->t.n_values;
+    if (nv == 0 || !M->payload) {   // an empty map: no lists, nothing to launch
+        M->rinfo.has_rows = 1;
+        if (info) *info = M->rinfo;
+        return CBX_OK;
+    }
+    if (!d_data || (in && (!in->rec_off || !in->rec_len || !in->segment)))
+        return fail(CBX_E_ARGUMENT, "cbx_key_map_index_rows: source arrays required");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_key_map_index_rows: n_rec records of rec_stride bytes exceed n_bytes");
+    struct Progs { KsfProg ksf; FilterProg flt; KmDevMap map; };
+    std::vector<Progs> progs(1);
+    memset((void*)progs.data(), 0, sizeof(Progs));
+    std::vector<GrpProg> probe(1);
+    const cbx_plan* P = M->plan;
+    rb = keyset_from_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, &M->probe_keys, Q->hfields.data(),
+                           (int32_t)Q->hfields.size(), Q->walk, source_keys, probe.data(), &progs[0].ksf, err);
+    if (rb != CBX_OK) return fail(rb, err);
+    if (source_filter) {
+        rb = filter_build(Q->hfields.data(), (int32_t)Q->hfields.size(), Q->walk, source_filter, &progs[0].flt, err);
+        if (rb != CBX_OK) return fail(rb, err);
+    }
+    // every kept source row with a non-null key is on at most one list
+    const int64_t cap = std::max<int64_t>(1, M->info.n_rows - M->info.n_null_rows);
+    struct RowsGuard {   // the lists are freed on every error path: the map stays a lookup map
+        cbx_key_map* m;
+        ~RowsGuard() {
+            if (!m) return;
+            if (m->row_mem) (void)hipFree(m->row_mem);
+            m->row_mem = nullptr; m->row_start = m->rows = nullptr;
+        }
+    } guard{M};
+    HIP_CHECK(hipMalloc(&M->row_mem, sizeof(int64_t) * (size_t)(nv + 1 + cap)));
+    M->row_start = (int64_t*)M->row_mem;
+    M->rows = M->row_start + nv + 1;
+    // block: programs | header | cursor (nv) | LDS list (nv) | global list (nv) | scan sums
+    const int64_t nb = scan64_sums_len(nv);
+    const size_t o_hdr = (sizeof(Progs) + 63) & ~(size_t)63;
+    const size_t o_cur = o_hdr + 8 * KR_WORDS;
+    const size_t o_l1 = o_cur + 8 * (size_t)nv;
+    const size_t o_l2 = o_l1 + 8 * (size_t)nv;
+    const size_t o_sums = o_l2 + 8 * (size_t)nv;
+    AsyncBlock ws(st);
+    HIP_CHECK(hipMallocAsync(&ws.p, o_sums + 8 * (size_t)nb, st));
+    uint8_t* b8 = (uint8_t*)ws.p;
+    KmDevMap& dm = progs[0].map;
+    dm.t = M->set->t;
+    dm.grp = (const CBX_CONST GrpProg*)(b8 + offsetof(Progs, ksf) + offsetof(KsfProg, src));
+    dm.first_row = M->first_row;
+    dm.n_rows = M->n_rows;
+    HIP_CHECK(hipMemcpyAsync(b8, progs.data(), sizeof(Progs), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(b8 + o_hdr, 0, 8 * KR_WORDS + 8 * (size_t)nv, st));   // the header and the cursors
+    HIP_CHECK(hipMemsetAsync(M->rows, 0xFF, sizeof(int64_t) * (size_t)cap, st));  // (a differing source leaves slots unwritten)
+    uint64_t* d_hdr = (uint64_t*)(b8 + o_hdr);
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    int64_t grid = std::min<int64_t>((n_tiles + kFltThreads / kWave - 1) / (kFltThreads / kWave), (int64_t)Q->num_cus * 8);
+    int64_t sort_grid = std::min<int64_t>(nv, (int64_t)Q->num_cus * 4);
+    if (max_workgroups > 0) { grid = std::min<int64_t>(grid, max_workgroups); sort_grid = std::min<int64_t>(sort_grid, max_workgroups); }
+    grid = std::max<int64_t>(grid, 1);
+    KmRowsArgs g{};
+    FilterArgs& a = g.a;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = source_filter ? (const CBX_CONST FilterProg*)(b8 + offsetof(Progs, flt)) : nullptr;
+    a.segmap = Q->opts.has_segments ? (const CBX_CONST cbx_segment_map*)Q->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)Q->d_fields;
+    a.lut = Q->d_lut;
+    g.map = (const CBX_CONST KmDevMap*)(b8 + offsetof(Progs, map));
+    g.has_filter = source_filter ? 1 : 0;
+    g.row_start = M->row_start;
+    g.cursor = (uint64_t*)(b8 + o_cur);
+    g.rows = M->rows;
+    g.cap = cap;
+    g.hdr = d_hdr;
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{Q};
+    if (Q->profiling) {
+        for (int k = 0; k < 2; k++) if (!(pe.e[k] = take_event(Q))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(pe.e[0], st));
+    }
+    int64_t* lds_list = (int64_t*)(b8 + o_l1);
+    int64_t* global_list = (int64_t*)(b8 + o_l2);
+    device_scan64(M->n_rows, nv, nullptr, M->row_start, (int64_t*)(b8 + o_sums), nullptr, st);
+    hipLaunchKernelGGL(keymap_rows_scatter_kernel, dim3((unsigned)grid), dim3(kFltThreads), 0, st, g);
+    hipLaunchKernelGGL(keymap_rows_classify_kernel, dim3(blocks_for(nv, 256)), dim3(256), 0, st, (const int64_t*)M->row_start, nv,
+                       M->rows, cap, lds_list, global_list, d_hdr);
+    hipLaunchKernelGGL(keymap_rows_sort_lds_kernel, dim3((unsigned)sort_grid), dim3(256), 0, st, (const int64_t*)M->row_start,
+                       (const int64_t*)lds_list, (const uint64_t*)(d_hdr + KR_N_LDS), M->rows);
+    hipLaunchKernelGGL(keymap_rows_sort_global_kernel, dim3((unsigned)sort_grid), dim3(256), 0, st, (const int64_t*)M->row_start,
+                       (const int64_t*)global_list, (const uint64_t*)(d_hdr + KR_N_GLOBAL), M->rows);
+    hipLaunchKernelGGL(keymap_rows_check_kernel, dim3(blocks_for(nv, 256)), dim3(256), 0, st, (const int64_t*)M->first_row,
+                       (const int64_t*)M->n_rows, (const int64_t*)M->row_start, (const uint64_t*)g.cursor,
+                       (const int64_t*)M->rows, cap, nv, d_hdr);
+    if (Q->profiling) HIP_CHECK(hipEventRecord(pe.e[1], st));
+    HIP_CHECK(hipGetLastError());
+    uint64_t hdr[KR_WORDS] = {};
+    HIP_CHECK(hipMemcpyAsync(hdr, d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));   // the only wait
+    if (hdr[KR_BAD_SLOTS] != 0 || hdr[KR_MISMATCH] != 0 || (int64_t)hdr[KR_TOTAL] > cap) return fail(CBX_E_STATE, kRowsSourceDiffers);
+    if (Q->profiling) HIP_CHECK(hipEventElapsedTime(&M->rinfo.index_ms, pe.e[0], pe.e[1]));
+    M->rinfo.has_rows = 1;
+    M->rinfo.n_indexed_rows = (int64_t)hdr[KR_TOTAL];
+    M->rinfo.n_lds = (int64_t)hdr[KR_N_LDS];
+    M->rinfo.n_global = (int64_t)hdr[KR_N_GLOBAL];
+    M->rinfo.n_short = nv - M->rinfo.n_lds - M->rinfo.n_global;
+    guard.m = nullptr;
+    if (info) *info = M->rinfo;
+    return CBX_OK;
+}
+
+// test (keymap_test_kernel over a (row_start, n_rows) view of the map) -> scan, compact, 64-bit scan -> one wait -> emit
+extern "C" int cbx_join_records_expand(cbx_plan* P, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                                       const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                                       int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                                       const cbx_key_set* const* sets, const int32_t* negate, int32_t n_sets,
+                                       const cbx_key_map* map, int32_t join_type, cbx_selection* out, int64_t out_capacity,
+                                       int64_t* n_out, int64_t* n_kept, int64_t* d_match, int64_t* d_fact_row, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!P || !n_out || !n_kept || n_rec < 0 || n_bytes < 0 || start_offset < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records_expand: invalid arguments");
+    *n_out = *n_kept = 0;
+    P->fx_ms[0] = P->fx_ms[1] = P->fx_ms[2] = 0.f;
+    P->last_fx = cbx_expand_info{};
+    P->last_fx.outputs_per_workgroup = kFxThreads;
+    const bool count_only = !out && out_capacity == 0;
+    std::string err;
+    int rc = km_join_check(map != nullptr, map && map->plan == P, join_type, count_only || d_match != nullptr, n_sets,
+                           sets != nullptr, err);
+    if (rc == CBX_OK) rc = fx_expand_check(map->rinfo.has_rows != 0, out != nullptr, out_capacity, err);
+    if (rc != CBX_OK) return fail(rc, err);
+    for (int s = 0; s < n_sets; s++) {
+        const std::string at = "cbx_join_records: set " + std::to_string(s) + ": ";
+        if (!sets[s]) return fail(CBX_E_ARGUMENT, at + "null");
+        if (sets[s]->plan != P) return fail(CBX_E_ARGUMENT, at + "built on another plan");
+        if (negate && negate[s] != 0 && sets[s]->t.n_keys != 1)
+            return fail(CBX_E_ARGUMENT, at + "only a single-column set may be negated");
+    }
+    const int n_src = (in ? 1 : 0) + ((d_rec_off || d_rec_len) ? 1 : 0) + (rec_stride > 0 ? 1 : 0);
+    if (n_src != 1 || (!in && !rec_stride && (!d_rec_off || !d_rec_len)) || rec_stride < 0)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: exactly one source (selection, framed records, record stride)");
+    const int L = P->opts.has_segments ? P->opts.segments.n_levels : 0;
+    if (!in && L > 0)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: a plan with Seg_Id levels filters a selection (cbx_select_records)");
+    struct Progs { FilterProg flt; KsDevSet sets[CBX_GROUP_MAX_KEYS]; KmDevMap map; };
+    std::vector<Progs> prog(1);
+    memset((void*)prog.data(), 0, sizeof(Progs));
+    if (filter) {
+        const int rb = filter_build(P->hfields.data(), (int32_t)P->hfields.size(), P->walk, filter, &prog[0].flt, err);
+        if (rb != CBX_OK) return fail(rb, err);
+    }
+    for (int s = 0; s < n_sets; s++) {
+        KsDevSet& d = prog[0].sets[s];
+        d.t = sets[s]->t;
+        d.grp = (const CBX_CONST GrpProg*)sets[s]->d_prog;
+        d.negate = negate && negate[s] != 0 ? 1 : 0;
+    }
+    // the view of the map the test pass probes: a member's "first row" is the start of its list (>= 0, so the verdict
+    // is the lookup join's), its "rows" the list's length
+    prog[0].map.t = map->set->t;
+    prog[0].map.grp = (const CBX_CONST GrpProg*)map->set->d_prog;
+    prog[0].map.first_row = map->row_start;   // (nullptr for an empty map: no probe ever hits)
+    prog[0].map.n_rows = map->n_rows;
+    if (in && out) out->file_id = in->file_id;
+    if (n_rec == 0) return CBX_OK;
+    if (!d_data || (out && (!out->rec_off || !out->rec_len || !out->record_id || !out->segment)) ||
+        (in && (!in->rec_off || !in->rec_len || !in->record_id || !in->segment)) ||
+        (in && L > 0 && (!in->seg_state || (out && !out->seg_state))))
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: selection arrays required");
+    if (in && out && (in->rec_off == out->rec_off || in->rec_len == out->rec_len || in->record_id == out->record_id ||
+                      in->segment == out->segment || (L > 0 && in->seg_state == out->seg_state)))
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: out must not share arrays with in");
+    if (rec_stride > 0 && n_rec > n_bytes / rec_stride)
+        return fail(CBX_E_ARGUMENT, "cbx_join_records: n_rec records of rec_stride bytes exceed n_bytes");
+    const int64_t n_tiles = (n_rec + kWave - 1) / kWave;
+    const int64_t nb = scan_sums_len(n_tiles + 1), nb64 = scan64_sums_len(n_rec);
+    // block: programs | keep words (n_tiles) | base (n_tiles + 1) | sums (nb) | list start (n_rec) | list length (n_rec) |
+    // kept ordinal (n_rec) | kept start (n_rec) | kept c (n_rec) | kept base (n_rec + 1) | sums64 (nb64) | header |
+    // counts (n_tiles + 2) | segments (n_rec)
+    const size_t o_keep = (sizeof(Progs) + 15) & ~(size_t)15;
+    const size_t o_base = o_keep + sizeof(uint64_t) * n_tiles;
+    const size_t o_sums = o_base + sizeof(int64_t) * (n_tiles + 1);
+    const size_t o_match = o_sums + sizeof(int64_t) * nb;
+    const size_t o_rows = o_match + sizeof(int64_t) * (size_t)n_rec;
+    const size_t o_kord = o_rows + sizeof(int64_t) * (size_t)n_rec;
+    const size_t o_kstart = o_kord + sizeof(int64_t) * (size_t)n_rec;
+    const size_t o_kc = o_kstart + sizeof(int64_t) * (size_t)n_rec;
+    const size_t o_kbase = o_kc + sizeof(int64_t) * (size_t)n_rec;
+    const size_t o_sums64 = o_kbase + sizeof(int64_t) * (size_t)(n_rec + 1);
+    const size_t o_hdr = o_sums64 + sizeof(int64_t) * (size_t)nb64;
+    const size_t o_cnt = o_hdr + sizeof(uint64_t) * FX_WORDS;
+    AsyncBlock blk(st);
+    const size_t o_seg = o_cnt + sizeof(uint32_t) * (n_tiles + 2);
+    const bool map_seg = !in && P->opts.has_segments;   // the active segment comes from the plan's segment map
+    HIP_CHECK(hipMallocAsync(&blk.p, o_seg + (map_seg ? sizeof(int16_t) * (size_t)n_rec : 0) + 16, st));
+    uint8_t* b8 = (uint8_t*)blk.p;
+    int64_t* base = (int64_t*)(b8 + o_base);
+    int64_t* sums = (int64_t*)(b8 + o_sums);
+    uint32_t* counts = (uint32_t*)(b8 + o_cnt);
+    uint64_t* d_hdr = (uint64_t*)(b8 + o_hdr);
+    HIP_CHECK(hipMemcpyAsync(b8, prog.data(), sizeof(Progs), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(counts + n_tiles, 0, sizeof(uint32_t), st));
+    HIP_CHECK(hipMemsetAsync(d_hdr, 0, sizeof(uint64_t) * FX_WORDS, st));
+    KsArgs g{};
+    FilterArgs& a = g.a;
+    a.data = d_data; a.n_bytes = n_bytes;
+    a.rec_off = in ? in->rec_off : d_rec_off;
+    a.rec_len = in ? in->rec_len : d_rec_len;
+    a.rec_seg = in ? in->segment : nullptr;
+    a.n = n_rec; a.n_tiles = n_tiles; a.stride = rec_stride; a.start_off = start_offset;
+    a.prog = (const CBX_CONST FilterProg*)b8;
+    a.segmap = P->opts.has_segments ? (const CBX_CONST cbx_segment_map*)P->d_segmap : nullptr;
+    a.fields = (const CBX_CONST Field*)P->d_fields;
+    a.lut = P->d_lut;
+    a.keep = (uint64_t*)(b8 + o_keep);
+    a.counts = counts;
+    a.seg_out = map_seg ? (int16_t*)(b8 + o_seg) : nullptr;
+    g.has_filter = filter ? 1 : 0;
+    g.n_sets = n_sets;
+    g.sets = (const CBX_CONST KsDevSet*)(b8 + offsetof(Progs, sets));
+    KmJoinArgs jn{};
+    jn.map = (const CBX_CONST KmDevMap*)(b8 + offsetof(Progs, map));
+    jn.match_tmp = (int64_t*)(b8 + o_match);
+    jn.rows_tmp = (int64_t*)(b8 + o_rows);
+    jn.join_type = join_type;
+    struct PassEvents {   // the events go back to the plan's pool on every exit path
+        cbx_plan* plan;
+        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~PassEvents() { for (hipEvent_t x : e) if (x) plan->ev_pool.push_back(x); }
+    } pe{P};
+    hipEvent_t* ev = pe.e;
+    if (P->profiling) {
+        for (int k = 0; k < 5; k++) if (!(ev[k] = take_event(P))) return fail(CBX_E_HIP, "hipEventCreate failed");
+        HIP_CHECK(hipEventRecord(ev[0], st));
+    }
+    const unsigned grid = blocks_for(n_tiles, kFltThreads / kWave);
+    hipLaunchKernelGGL(keymap_test_kernel, dim3(grid), dim3(kFltThreads), 0, st, g, jn);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[1], st));
+    device_scan(counts, n_tiles + 1, base, sums, st);
+    int64_t* kept_base = (int64_t*)(b8 + o_kbase);
+    hipLaunchKernelGGL(fanout_compact_kernel, dim3(grid), dim3(kFltThreads), 0, st, (const uint64_t*)a.keep, (const int64_t*)base,
+                       n_tiles, (const int64_t*)jn.match_tmp, (const int64_t*)jn.rows_tmp, join_type, (int64_t*)(b8 + o_kord),
+                       (int64_t*)(b8 + o_kstart), (int64_t*)(b8 + o_kc), d_hdr);
+    // the kept count stays on the device: the grid covers n_rec
+    device_scan64((const int64_t*)(b8 + o_kc), n_rec, (const int64_t*)(base + n_tiles), kept_base, (int64_t*)(b8 + o_sums64),
+                  d_hdr + FX_TOTAL, st);
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[2], st));
+    HIP_CHECK(hipGetLastError());
+    uint64_t hdr[FX_WORDS] = {};
+    HIP_CHECK(hipMemcpyAsync(hdr, d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));   // the only wait: T, the kept count and the largest c together
+    const int64_t T = (int64_t)hdr[FX_TOTAL], kept = (int64_t)hdr[FX_N_KEPT];
+    *n_out = T;
+    *n_kept = kept;
+    P->last_fx.n_kept = kept;
+    P->last_fx.n_out = T;
+    P->last_fx.max_fanout = (int64_t)hdr[FX_MAX_C];
+    P->last_fx.host_waits = 1;
+    if (P->profiling)
+        for (int k = 0; k < 2; k++) HIP_CHECK(hipEventElapsedTime(&P->fx_ms[k], ev[k], ev[k + 1]));
+    if (count_only) return CBX_OK;
+    if (T > out_capacity) return fail(CBX_E_CAPACITY, fx_capacity_message(T, out_capacity));
+    if (T == 0) return CBX_OK;
+    const int64_t emit_grid = (T + kFxThreads - 1) / kFxThreads;
+    if (emit_grid > 0x7FFFFFFFll) return fail(CBX_E_ARGUMENT, "cbx_join_records_expand: " + std::to_string(T) + " output rows exceed one launch");
+    FxEmitArgs e{};
+    e.a = a;
+    e.kept_base = kept_base;
+    e.kept_ord = (const int64_t*)(b8 + o_kord);
+    e.kept_start = (const int64_t*)(b8 + o_kstart);
+    e.rows = map->rows;
+    e.n_kept = kept; e.n_out = T; e.n_indexed = map->rinfo.n_indexed_rows; e.first_record_id = first_record_id;
+    cbx_selection none{};
+    e.in = in ? *in : none;
+    e.out = *out;
+    e.has_in = in ? 1 : 0;
+    e.n_state = L > 0 ? 1 + L : 0;
+    e.d_match = d_match;
+    e.d_fact_row = d_fact_row;
+    if (P->profiling) HIP_CHECK(hipEventRecord(ev[3], st));
+    hipLaunchKernelGGL(fanout_emit_kernel, dim3((unsigned)emit_grid), dim3(kFxThreads), 0, st, e);
+    HIP_CHECK(hipGetLastError());
+    P->last_fx.emit_grid = emit_grid;
+    if (P->profiling) {   // (a second wait, only to read the emit's duration)
+        HIP_CHECK(hipEventRecord(ev[4], st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipEventElapsedTime(&P->fx_ms[2], ev[3], ev[4]));
+        P->last_fx.host_waits = 2;
+    }
+    return CBX_OK;
+}
+
+extern "C" int cbx_join_expand_info(cbx_plan* P, cbx_expand_info* out) {
+    if (!P || !out) return fail(CBX_E_ARGUMENT, "cbx_join_expand_info: invalid arguments");
+    *out = P->last_fx;
+    return CBX_OK;
+}
+
+extern "C" int cbx_join_expand_pass_times(cbx_plan* P, float* test_ms, float* scan_ms, float* emit_ms) {
+    if (!P) return fail(CBX_E_ARGUMENT, "null plan");
+    if (test_ms) *test_ms = P->fx_ms[0];
+    if (scan_ms) *scan_ms = P->fx_ms[1];
+    if (emit_ms) *emit_ms = P->fx_ms[2];
     return CBX_OK;
 }
 

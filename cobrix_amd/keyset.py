@@ -241,14 +241,28 @@ class DuplicateKeys(Exception):
         self.max_rows_per_key = max_rows_per_key
 
 
+class JoinOverflow(Exception):
+    """A fan-out join (duplicates="all") whose output has more rows than `max_rows` allows."""
+
+    def __init__(self, needed: int, max_rows: int):
+        super().__init__(f"the join has {needed} output rows, more than max_rows={max_rows}: raise max_rows, or size the "
+                         "output with join_count first")
+        self.needed = needed
+        self.max_rows = max_rows
+
+
 def check_join(plan, key_map, how: str, duplicates: str) -> int:
     """The join type (`native.JOIN_INNER` / `JOIN_LEFT`) of a join of `plan`'s rows against `key_map`, after every
     refusal that needs no device: an unknown `how` or `duplicates`, a closed map, a map built for another reader's
-    plan, and -- with duplicates="error" -- `DuplicateKeys` when the dimension has a key on more than one row."""
+    plan, and -- with duplicates="error" -- `DuplicateKeys` when the dimension has a key on more than one row.
+    duplicates="all" is the fan-out join: one output row per matching dimension row."""
     if how not in ("inner", "left"):
         raise ValueError(f"join: how={how!r} is neither 'inner' nor 'left' (a lookup join has no right or full form)")
-    if duplicates not in ("error", "first"):
-        raise ValueError(f"join: duplicates={duplicates!r} is neither 'error' nor 'first'")
+    if duplicates not in ("error", "first", "all"):
+        raise ValueError(f"join: duplicates={duplicates!r} is neither 'error' nor 'first' nor 'all'")
+    if duplicates == "all" and not hasattr(key_map, "index_rows"):
+        raise ValueError("join: duplicates='all' takes a key map that can carry row lists (KeyMap.index_rows); for this "
+                         "map it is neither 'error' nor 'first'")
     if key_map.closed:
         raise ValueError("the key map is closed")
     if key_map.plan is not plan:
@@ -256,6 +270,20 @@ def check_join(plan, key_map, how: str, duplicates: str) -> int:
     if duplicates == "error" and key_map.n_duplicate_keys > 0:
         raise DuplicateKeys(key_map.n_duplicate_keys, key_map.max_rows_per_key)
     return N.JOIN_INNER if how == "inner" else N.JOIN_LEFT
+
+
+class _DeviceInt64:
+    """n int64 values at a device address, for torch.as_tensor (the CUDA array interface)."""
+
+    def __init__(self, ptr: int, n: int):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i8", "data": (ptr, False), "version": 2}
+
+
+def _device_view(torch, ptr: int, n: int):
+    """A copy of n int64 values at device address `ptr` as a tensor of its own."""
+    if n <= 0:
+        return torch.empty(0, dtype=torch.int64, device="cuda")
+    return torch.as_tensor(_DeviceInt64(ptr, n), device="cuda").clone()
 
 
 class _KeySetView(KeySet):
@@ -313,6 +341,11 @@ class KeyMap:
         self.source_data = None
         self.source_bytes = 0
         self.source = None
+        # what index_rows presents again: the source's key table, its filter table, its handle and the call's bounds
+        self._source_table, self._source_handle = stable, source_handle
+        self._source_filter, self._start_offset = filter_table, start_offset
+        self._n_rec, self._n_bytes, self._data_ptr = n_rec, n_bytes, d_data_ptr
+        self._sel_struct, self._rec_off_ptr, self._rec_len_ptr, self._stride = sel_struct, rec_off_ptr, rec_len_ptr, stride
         ks = _KeySetView.__new__(_KeySetView)
         ks.plan, ks.names = probe_plan, list(names)
         ks.dropped, ks.has_null, ks.n_values = self.dropped, self.has_null, self.n_values
@@ -325,12 +358,57 @@ class KeyMap:
     def closed(self) -> bool:
         return self.handle is None
 
+    def rows_info(self) -> N.CbxKeymapRowsInfo:
+        """has_rows, n_indexed_rows, the members each sort path took (n_short / n_lds / n_global), the two boundaries
+        (short_max / lds_max) and index_ms (profiling on) of the row lists (`cbx_key_map_rows_info`)."""
+        if self.closed:
+            raise ValueError("the key map is closed")
+        out = N.CbxKeymapRowsInfo()
+        N.check(N.load().cbx_key_map_rows_info(self.handle, ctypes.byref(out)))
+        return out
+
+    @property
+    def has_rows(self) -> bool:
+        """Whether the map carries per-key row lists (`index_rows`)."""
+        return not self.closed and bool(self.rows_info().has_rows)
+
+    def index_rows(self, max_workgroups: int = 0, stream=None) -> N.CbxKeymapRowsInfo:
+        """`cbx_key_map_index_rows`: per member the ascending list of ALL its source rows, which a fan-out join
+        (duplicates="all") walks.  Presents the retained source again (the device bytes the map references must be
+        unchanged); idempotent: a second call launches nothing.  8 bytes per kept source row plus 8 per value, freed
+        with the map."""
+        if self.closed:
+            raise ValueError("the key map is closed")
+        info = N.CbxKeymapRowsInfo()
+        N.check(N.load().cbx_key_map_index_rows(
+            self.handle, self._source_handle, ctypes.byref(self._source_table), self._data_ptr, self._n_bytes,
+            ctypes.byref(self._sel_struct) if self._sel_struct is not None else None, self._rec_off_ptr, self._rec_len_ptr,
+            self._n_rec, self._stride, self._start_offset,
+            ctypes.byref(self._source_filter) if self._source_filter is not None else None, max_workgroups,
+            ctypes.c_void_p(stream.cuda_stream if stream is not None else 0), ctypes.byref(info)))
+        return info
+
+    def row_lists(self):
+        """(row_start, rows): int64 device tensors over the map's memory (valid until close) -- rows[row_start[v] :
+        row_start[v + 1]] are member v's source ordinals, ascending.  (None, None) before `index_rows` and for an
+        empty map."""
+        if self.closed:
+            raise ValueError("the key map is closed")
+        a, b = ctypes.c_void_p(), ctypes.c_void_p()
+        N.check(N.load().cbx_key_map_rows(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        if not a.value:
+            return None, None
+        import torch
+        n = self.rows_info().n_indexed_rows
+        return _device_view(torch, a.value, self.n_values + 1), _device_view(torch, b.value, n)
+
     def close(self) -> None:
         if self.handle is not None:
             self.key_set.close()
             N.load().cbx_key_map_destroy(self.handle)
             self.handle = None
             self.source_reader = self.source_data = self.source = None
+            self._sel_struct = self._source_filter = None
 
     def __enter__(self) -> "KeyMap":
         return self

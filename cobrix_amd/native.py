@@ -52,7 +52,9 @@ EXPORTED_SYMBOLS = ("cbx_abi_version", "cbx_last_error", "cbx_plan_create", "cbx
                     "cbx_key_set_create_from_records",
                     "cbx_filter_max_op",
                     "cbx_key_map_create_from_records", "cbx_key_map_info", "cbx_key_map_destroy", "cbx_key_map_set",
-                    "cbx_join_records", "cbx_select_ordinals", "cbx_join_pass_times")
+                    "cbx_join_records", "cbx_select_ordinals", "cbx_join_pass_times",
+                    "cbx_key_map_index_rows", "cbx_key_map_rows_info", "cbx_key_map_rows", "cbx_join_records_expand",
+                    "cbx_join_expand_info", "cbx_join_expand_pass_times")
 # grouped aggregates were an additive extension of ABI 24: the symbols are required
 GROUP_SYMBOLS = ("cbx_group_layout", "cbx_aggregate_grouped", "cbx_group_pass_times")
 # Top-N / LIMIT pushdown was an additive extension of ABI 25: the symbols are required
@@ -66,6 +68,10 @@ FILTER_STRING_SYMBOLS = ("cbx_filter_max_op",)
 # lookup joins (key maps, the join stage, rows by ordinal) were an additive extension of ABI 25: the symbols are required
 KEYMAP_SYMBOLS = ("cbx_key_map_create_from_records", "cbx_key_map_info", "cbx_key_map_destroy", "cbx_key_map_set",
                   "cbx_join_records", "cbx_select_ordinals", "cbx_join_pass_times")
+# fan-out joins (row lists on a key map, the expanding join stage) were an additive extension of ABI 25: the symbols
+# are required
+FANOUT_SYMBOLS = ("cbx_key_map_index_rows", "cbx_key_map_rows_info", "cbx_key_map_rows", "cbx_join_records_expand",
+                  "cbx_join_expand_info", "cbx_join_expand_pass_times")
 ABI_VERSION = 25
 
 
@@ -282,6 +288,19 @@ class CbxKeymapInfo(ctypes.Structure):
 JOIN_INNER, JOIN_LEFT = 0, 1
 
 
+class CbxKeymapRowsInfo(ctypes.Structure):
+    """cbx_key_map_rows_info: the row lists of a key map and how their sort ran."""
+    _fields_ = [("n_indexed_rows", ctypes.c_int64), ("n_short", ctypes.c_int64), ("n_lds", ctypes.c_int64),
+                ("n_global", ctypes.c_int64), ("has_rows", ctypes.c_int32), ("short_max", ctypes.c_int32),
+                ("lds_max", ctypes.c_int32), ("index_ms", ctypes.c_float)]
+
+
+class CbxJoinExpandInfo(ctypes.Structure):
+    """cbx_join_expand_info: how the last cbx_join_records_expand call ran."""
+    _fields_ = [("n_kept", ctypes.c_int64), ("n_out", ctypes.c_int64), ("max_fanout", ctypes.c_int64),
+                ("emit_grid", ctypes.c_int64), ("outputs_per_workgroup", ctypes.c_int32), ("host_waits", ctypes.c_int32)]
+
+
 W_GROUP, W_PRIM = 0, 1
 W_REDEFINED, W_REDEFINES = 0x1, 0x2
 
@@ -441,7 +460,14 @@ def load():
                      ("cbx_key_map_set", [P]),
                      ("cbx_join_records", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, i32, P, i32, P, P, P, P, P]),
                      ("cbx_select_ordinals", [P, P, i64, P, P, P, i64, i32, i32, i64, P, i64, P, P]),
-                     ("cbx_join_pass_times", [P, P, P, P])):
+                     ("cbx_join_pass_times", [P, P, P, P]),
+                     ("cbx_key_map_index_rows", [P, P, P, P, i64, P, P, P, i64, i32, i32, P, i32, P, P]),
+                     ("cbx_key_map_rows_info", [P, P]),
+                     ("cbx_key_map_rows", [P, P, P]),
+                     ("cbx_join_records_expand", [P, P, i64, P, P, P, i64, i32, i32, i64, P, P, P, i32, P, i32, P, i64, P, P,
+                                                  P, P, P]),
+                     ("cbx_join_expand_info", [P, P]),
+                     ("cbx_join_expand_pass_times", [P, P, P, P])):
         if hasattr(L, name):   # (diagnostic builds of older revisions lack the newest entry points)
             getattr(L, name).argtypes = at
     if L.cbx_abi_version() != ABI_VERSION and not os.environ.get("CBX_LIB_VARIANT"):
@@ -466,6 +492,9 @@ def load():
     missing = [n for n in KEYMAP_SYMBOLS if not hasattr(L, n)]
     if missing and not os.environ.get("CBX_LIB_VARIANT"):
         raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (lookup joins); rebuild it")
+    missing = [n for n in FANOUT_SYMBOLS if not hasattr(L, n)]
+    if missing and not os.environ.get("CBX_LIB_VARIANT"):
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {ABI_VERSION} without {', '.join(missing)} (fan-out joins); rebuild it")
     if hasattr(L, "cbx_key_set_destroy"):
         L.cbx_key_set_destroy.restype = None
     if hasattr(L, "cbx_key_map_destroy"):

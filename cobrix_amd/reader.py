@@ -25,7 +25,11 @@ from .aggregate import (AggregateResult, GroupedAggregateResult, GroupOverflow, 
                         compile_group_by)
 from .aggregate import Unhandled as AggregateUnhandled
 from .filter import compile_filters_with_sets
-from .keyset import KeyMap, KeySet, check_join
+from .keyset import JoinOverflow, KeyMap, KeySet, check_join
+
+# the default bound on a fan-out join's output rows (duplicates="all"): 40 bytes of selection, match and fact-row
+# arrays per row, so 2.5 GiB at the bound
+JOIN_MAX_ROWS = 1 << 26
 from .plan import DecodePlan, NativePlan, NeedsWalk, build_plan
 from .topn import compile_order
 from .schema import ST_DECIMAL, spark_schema
@@ -1147,16 +1151,24 @@ class _BaseReader:
 
     def _join_records(self, key_map: KeyMap, how: str, filters, duplicates: str, d_data, n_bytes: int, n_rec: int, st, *,
                       sel=None, rec_off=None, rec_len=None, stride: int = 0, first_record_id: int = 0,
-                      file_id: int = 0, decode: bool = True) -> "JoinResult":
+                      file_id: int = 0, decode: bool = True, max_rows: Optional[int] = None,
+                      count_only: bool = False):
         """cbx_join_records over one source through the full plan, then the decode of the kept rows.  All or nothing:
         `keyset.DuplicateKeys` (duplicates="error") and a filter that is not pushed down raise before any launch.
-        decode=False: `batch` is None (timing tools)."""
+        decode=False: `batch` is None (timing tools).
+        duplicates="all": cbx_join_records_expand -- the row lists are built on first use, the output is sized n_rec
+        first (exact for a unique dimension) and once more with the reported size when that is too small and at most
+        `max_rows` (default JOIN_MAX_ROWS), else `keyset.JoinOverflow`.  count_only: (n_out, n_kept), nothing emitted."""
         join_type = check_join(self.plan, key_map, how, duplicates)
         table, sets, negate = None, [], []
         if filters:
             table, sets, negate, unhandled = compile_filters_with_sets(self.plan, filters)
             if unhandled:
                 raise AggregateUnhandled(f"filter {unhandled[0]!r} is not evaluated on the GPU: {unhandled.reasons[0]}")
+        if duplicates == "all":
+            return self._join_expand(key_map, how, join_type, table, sets, negate, d_data, n_bytes, n_rec, st, sel=sel,
+                                     rec_off=rec_off, rec_len=rec_len, stride=stride, first_record_id=first_record_id,
+                                     file_id=file_id, decode=decode, max_rows=max_rows, count_only=count_only)
         torch = _torch()
         out, cs = self._empty_selection(n_rec, d_data.device)
         cs.file_id = sel["struct"].file_id if sel is not None else file_id
@@ -1181,6 +1193,69 @@ class _BaseReader:
             batch = self._decode_rows(d_data, n_bytes, out, st)
             batch.unhandled_filters = []
         return JoinResult(key_map, how, batch, out, match[:ns.value], match_rows[:ns.value], st)
+
+    def _join_expand(self, key_map: KeyMap, how: str, join_type: int, table, sets, negate, d_data, n_bytes: int, n_rec: int,
+                     st, *, sel=None, rec_off=None, rec_len=None, stride: int = 0, first_record_id: int = 0, file_id: int = 0,
+                     decode: bool = True, max_rows: Optional[int] = None, count_only: bool = False):
+        """cbx_join_records_expand (see `_join_records`): one output row per (kept fact row, matching dimension row)."""
+        torch = _torch()
+        max_rows = JOIN_MAX_ROWS if max_rows is None else int(max_rows)
+        if not key_map.has_rows:
+            key_map.index_rows(stream=st)
+        L = N.load()
+        handles = (ctypes.c_void_p * max(1, len(sets)))(*[s.handle for s in sets])
+        neg = (ctypes.c_int32 * max(1, len(sets)))(*negate)
+        n_out, n_kept = ctypes.c_int64(0), ctypes.c_int64(0)
+
+        def call(cap, cs, match, fact):
+            return L.cbx_join_records_expand(
+                self.native.handle, d_data.data_ptr(), n_bytes, ctypes.byref(sel["struct"]) if sel is not None else None,
+                rec_off.data_ptr() if rec_off is not None else None, rec_len.data_ptr() if rec_len is not None else None,
+                n_rec, stride, self.params.start_offset, first_record_id, ctypes.byref(table) if table is not None else None,
+                ctypes.addressof(handles) if sets else None, ctypes.addressof(neg) if sets else None, len(sets),
+                key_map.handle, join_type, ctypes.byref(cs) if cs is not None else None, cap, ctypes.byref(n_out),
+                ctypes.byref(n_kept), match.data_ptr() if match is not None else None,
+                fact.data_ptr() if fact is not None else None, ctypes.c_void_p(st.cuda_stream))
+
+        if count_only:
+            N.check(call(0, None, None, None))
+            return n_out.value, n_kept.value
+        cap = n_rec
+        for attempt in (0, 1):
+            out, cs = self._empty_selection(cap, d_data.device)
+            cs.file_id = sel["struct"].file_id if sel is not None else file_id
+            match = torch.empty(max(1, cap), dtype=torch.int64, device=d_data.device)
+            fact = torch.empty(max(1, cap), dtype=torch.int64, device=d_data.device)
+            rc = call(cap, cs, match, fact)
+            if rc != N.CBX_E_CAPACITY or attempt == 1:
+                N.check(rc)
+                break
+            if n_out.value > max_rows:
+                raise JoinOverflow(n_out.value, max_rows)
+            cap = n_out.value   # the exact size, from the call that did not fit
+        out["n"] = n_out.value
+        out["struct"] = cs
+        out["source"] = sel
+        out["unhandled"] = []
+        batch = None
+        if decode:
+            batch = self._decode_rows(d_data, n_bytes, out, st)
+            batch.unhandled_filters = []
+        return JoinResult(key_map, how, batch, out, match[:n_out.value], None, st, fact_row=fact[:n_out.value],
+                          n_kept=n_kept.value)
+
+    def join_expand_info(self) -> N.CbxJoinExpandInfo:
+        """How the last duplicates="all" join ran (cbx_join_expand_info): n_kept, n_out, the largest fan-out, the emit
+        grid, outputs per workgroup, host waits."""
+        info = N.CbxJoinExpandInfo()
+        N.check(N.load().cbx_join_expand_info(self.native.handle, ctypes.byref(info)))
+        return info
+
+    def join_expand_pass_times(self) -> Tuple[float, float, float]:
+        """(test, scan, emit) ms of the last duplicates="all" join (cbx_plan_set_profiling on; zeros otherwise)."""
+        t, s_, e = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
+        N.check(N.load().cbx_join_expand_pass_times(self.native.handle, ctypes.byref(t), ctypes.byref(s_), ctypes.byref(e)))
+        return t.value, s_.value, e.value
 
     def join_pass_times(self) -> Tuple[float, float, float]:
         """(test, scan, emit) ms of the last join call (cbx_plan_set_profiling on; zeros otherwise)."""
@@ -1263,11 +1338,21 @@ class JoinResult:
     `batch`: the kept fact rows, decoded (in source order); `selection`: their selection; `match`: int64 device
     tensor, per kept row the ordinal of the first dimension row with its key or -1; `matched`: match >= 0;
     `match_rows`: how many dimension rows had that key (0 where unmatched).  With `n_duplicate_keys == 0` on the map
-    this is SQL's inner / left join; with duplicates the first dimension row stands for all of them."""
+    this is SQL's inner / left join; with duplicates the first dimension row stands for all of them.
 
-    def __init__(self, key_map: KeyMap, how: str, batch: DecodedBatch, selection: Dict[str, Any], match, match_rows, stream):
+    With duplicates="all" (the fan-out join) this IS SQL's inner / left join whatever the dimension holds: there is one
+    output row per (kept fact row, matching dimension row), a kept fact row's outputs are consecutive and in the
+    order of the dimension, `batch` / `selection` repeat the fact row once per match, `match` is the ordinal of that
+    output's dimension row (-1 for the single row of an unmatched LEFT row), `fact_row` (int64 device tensor, one
+    entry per output row; None for a lookup join) the fact row's ordinal in the input, `n_kept` the number of fact
+    rows with at least one output, and `match_rows` is None."""
+
+    def __init__(self, key_map: KeyMap, how: str, batch: DecodedBatch, selection: Dict[str, Any], match, match_rows, stream,
+                 fact_row=None, n_kept: Optional[int] = None):
         self.key_map, self.how, self.batch, self.selection = key_map, how, batch, selection
         self.match, self.match_rows = match, match_rows
+        self.fact_row = fact_row
+        self.n_kept = selection["n"] if n_kept is None else n_kept
         self.matched = match >= 0
         self._stream = stream
 
@@ -1527,25 +1612,43 @@ class FixedLenNestedReader(_BaseReader):
         return self.key_map_of_device(t, len(data), source_names, probe, names, filters, max_values)
 
     def join_device(self, d_data, n_bytes: int, key_map: KeyMap, how: str = "inner", filters=None, duplicates: str = "error",
-                    first_record_id: int = 0, stream=None) -> JoinResult:
+                    first_record_id: int = 0, stream=None, max_rows: Optional[int] = None) -> JoinResult:
         """A broadcast lookup join of this (fact) reader's rows against a key map built for it: the rows `filters`
         keep whose key is a member (how="inner") or all of them (how="left"), each with the ordinal of its dimension
         row (`JoinResult`).  duplicates="error" raises `keyset.DuplicateKeys` when the dimension has a key on more
-        than one row; duplicates="first" takes the first such row.  A filter that is not pushed down raises
-        `aggregate.Unhandled`, as in the other all-or-nothing stages."""
+        than one row; duplicates="first" takes the first such row; duplicates="all" is the fan-out join, SQL's inner /
+        left join: one output row per matching dimension row, at most `max_rows` of them (default JOIN_MAX_ROWS,
+        2^26; more raises `keyset.JoinOverflow`).  A filter that is not pushed down raises `aggregate.Unhandled`, as
+        in the other all-or-nothing stages."""
         torch = _torch()
         stride = self.get_record_size()
         st = stream if stream is not None else torch.cuda.current_stream()
         return self._join_records(key_map, how, filters, duplicates, d_data, n_bytes, n_bytes // stride, st, stride=stride,
-                                  first_record_id=first_record_id)
+                                  first_record_id=first_record_id, max_rows=max_rows)
 
     def join(self, data: bytes, key_map: KeyMap, how: str = "inner", filters=None, duplicates: str = "error",
-             first_record_id: int = 0) -> JoinResult:
+             first_record_id: int = 0, max_rows: Optional[int] = None) -> JoinResult:
         """`join_device` over host bytes, with the file-size checks of `decode`."""
         torch = _torch()
         self.check_binary_data_validity(len(data))
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
-        return self.join_device(t, len(data), key_map, how, filters, duplicates, first_record_id)
+        return self.join_device(t, len(data), key_map, how, filters, duplicates, first_record_id, max_rows=max_rows)
+
+    def join_count_device(self, d_data, n_bytes: int, key_map: KeyMap, how: str = "inner", filters=None, stream=None):
+        """(n_out, n_kept) of `join_device(..., duplicates="all")` without emitting a row: the join's COUNT(*) and the
+        number of fact rows with at least one output (the count-only form of cbx_join_records_expand)."""
+        torch = _torch()
+        stride = self.get_record_size()
+        st = stream if stream is not None else torch.cuda.current_stream()
+        return self._join_records(key_map, how, filters, "all", d_data, n_bytes, n_bytes // stride, st, stride=stride,
+                                  count_only=True)
+
+    def join_count(self, data: bytes, key_map: KeyMap, how: str = "inner", filters=None):
+        """`join_count_device` over host bytes, with the file-size checks of `decode`."""
+        torch = _torch()
+        self.check_binary_data_validity(len(data))
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda") if len(data) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        return self.join_count_device(t, len(data), key_map, how, filters)
 
     def top_n_device(self, d_data, n_bytes: int, orders, limit: int, filters=None, first_record_id: int = 0,
                      stream=None, max_workgroups: int = 0) -> DecodedBatch:
@@ -2440,31 +2543,47 @@ class VarLenNestedReader(_BaseReader):
         return self.key_map_of_device(t, vb, sel, source_names, probe, names, filters, max_values, file_id)
 
     def join_device(self, d_data, n_bytes: int, sel_or_framing, key_map: KeyMap, how: str = "inner", filters=None,
-                    duplicates: str = "error", first_record_id: int = 0, file_id: int = 0, stream=None) -> JoinResult:
+                    duplicates: str = "error", first_record_id: int = 0, file_id: int = 0, stream=None,
+                    max_rows: Optional[int] = None, count_only: bool = False) -> JoinResult:
         """A broadcast lookup join of a selection or framed records of this (fact) reader against a key map built
-        for it; see `FixedLenNestedReader.join_device`.  A reader with segment id levels takes a selection only, as
-        `filter`; hierarchical reads refuse."""
+        for it; see `FixedLenNestedReader.join_device` (duplicates="all" and `max_rows` included).  A reader with
+        segment id levels takes a selection only, as `filter`; hierarchical reads refuse."""
         if self.hierarchical:
             raise N.CbxError(N.CBX_E_UNSUPPORTED, "joins on a hierarchical read: rows are trees of segments")
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream()
         if isinstance(sel_or_framing, dict):
             return self._join_records(key_map, how, filters, duplicates, d_data, n_bytes, sel_or_framing["n"], st,
-                                      sel=sel_or_framing)
+                                      sel=sel_or_framing, max_rows=max_rows, count_only=count_only)
         if self.plan.seg_id_columns:
             raise N.CbxError(N.CBX_E_ARGUMENT, "join: a reader with segment id levels takes a selection "
                                                "(the Seg_IdN state comes from select()); pass select()'s result")
         rec_off, rec_len = sel_or_framing
         return self._join_records(key_map, how, filters, duplicates, d_data, n_bytes, int(rec_off.numel()), st,
-                                  rec_off=rec_off, rec_len=rec_len, first_record_id=first_record_id, file_id=file_id)
+                                  rec_off=rec_off, rec_len=rec_len, first_record_id=first_record_id, file_id=file_id,
+                                  max_rows=max_rows, count_only=count_only)
 
     def join(self, data: bytes, key_map: KeyMap, how: str = "inner", filters=None, duplicates: str = "error",
-             first_record_id: int = 0, file_id: int = 0) -> JoinResult:
+             first_record_id: int = 0, file_id: int = 0, max_rows: Optional[int] = None) -> JoinResult:
         """`join_device` over a whole file: of the rows `read(data, filters=filters)` would return."""
         if self.hierarchical:
             raise N.CbxError(N.CBX_E_UNSUPPORTED, "joins on a hierarchical read: rows are trees of segments")
         t, vb, sel = self._whole_file_selection(data, file_id)
-        return self.join_device(t, vb, sel, key_map, how, filters, duplicates, first_record_id, file_id)
+        return self.join_device(t, vb, sel, key_map, how, filters, duplicates, first_record_id, file_id, max_rows=max_rows)
+
+    def join_count_device(self, d_data, n_bytes: int, sel_or_framing, key_map: KeyMap, how: str = "inner", filters=None,
+                          stream=None):
+        """(n_out, n_kept) of `join_device(..., duplicates="all")` without emitting a row (the join's COUNT(*))."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "joins on a hierarchical read: rows are trees of segments")
+        return self.join_device(d_data, n_bytes, sel_or_framing, key_map, how, filters, "all", stream=stream, count_only=True)
+
+    def join_count(self, data: bytes, key_map: KeyMap, how: str = "inner", filters=None, file_id: int = 0):
+        """`join_count_device` over a whole file."""
+        if self.hierarchical:
+            raise N.CbxError(N.CBX_E_UNSUPPORTED, "joins on a hierarchical read: rows are trees of segments")
+        t, vb, sel = self._whole_file_selection(data, file_id)
+        return self.join_count_device(t, vb, sel, key_map, how, filters)
 
     def top_n_device(self, d_data, n_bytes: int, sel_or_framing, orders, limit: int, filters=None,
                      first_record_id: int = 0, file_id: int = 0, stream=None, max_workgroups: int = 0) -> DecodedBatch:

@@ -964,6 +964,83 @@ int cbx_select_ordinals(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, 
  * events while cbx_plan_set_profiling is on. */
 int cbx_join_pass_times(cbx_plan* plan, float* test_ms, float* scan_ms, float* emit_ms);
 
+/* ---- fan-out joins: one output row per match (an additive extension of ABI 25; cbx_keymap_rows.h) ----
+ *
+ * Row lists.  cbx_key_map_index_rows gives an existing map, for every member v, rows[row_start[v] .. row_start[v+1]):
+ * the ordinals of ALL source rows source_filter keeps whose key is v, ASCENDING, numbered as first_row is.  So
+ * rows[row_start[v]] == first_row[v], row_start[v+1] - row_start[v] == n_rows[v] and row_start[n_values] is the sum
+ * of n_rows.  Nothing depends on the grid, on max_workgroups or on timing.  The map does not keep its source: the
+ * caller presents it again -- source_plan, source_keys, the record source and source_filter exactly as
+ * cbx_key_map_create_from_records took them.  source_plan and n_rec must be the map's (CBX_E_ARGUMENT, no launch);
+ * a source that differs otherwise never writes outside a member's segment and is found by the check pass:
+ * CBX_E_STATE "source differs from the one the map was built from", the lists are freed and the map stays a valid
+ * lookup map.  A second call on a map with lists is CBX_OK and launches nothing; so is a call on an empty map.
+ * Passes: a 64-bit exclusive scan of n_rows; scatter (the fill pass's geometry and probe, one 64-bit atomic add on a
+ * per-member cursor per hit); sort -- segments of up to short_max ordinals by one lane each, up to lds_max by one
+ * workgroup through LDS, longer ones by one workgroup in global memory (slow, never refused); check (one lane per
+ * value).  Host waits: one.  Memory: 8 bytes per kept source row plus 8 per value, owned by the map, freed by
+ * cbx_key_map_destroy; 24 bytes per value from the stream's pool during the call.
+ *
+ * Expand.  cbx_join_records_expand takes cbx_join_records' arguments; K(r) and the member j(r) are as there, L(r) is
+ * that member's row list (empty when j(r) = -1).  INNER: c(r) = |L(r)| when K(r), else 0.  LEFT: c(r) = max(|L(r)|, 1)
+ * when K(r), else 0.  T = sum of c(r), in 64 bits.  The outputs of r occupy [B(r), B(r) + c(r)), B the exclusive
+ * prefix of c in source order; output row B(r) + q has the selection row filter_emit_kernel writes for r (`out`),
+ * d_match = L(r)[q] or -1 for the single row of an unmatched LEFT row, and d_fact_row (may be NULL) = r's ordinal in
+ * the input.  *n_out = T, *n_kept = the number of r with c(r) > 0.  On a map with n_duplicate_keys == 0, `out`,
+ * *n_out and d_match are bit-identical to cbx_join_records' out, *n_selected and d_match.  WITH ROW LISTS THIS IS
+ * SQL'S INNER / LEFT JOIN.  T > out_capacity: CBX_E_CAPACITY with *n_out = T and *n_kept set, both numbers in the
+ * message, and NO output array written (the emit is not launched).  out == NULL with out_capacity == 0 is the
+ * count-only form (the join's COUNT(*)): the two numbers, CBX_OK, d_match / d_fact_row unused.  A map without row
+ * lists: CBX_E_STATE.  Every other refusal is cbx_join_records' own, message for message.  n_rec == 0 launches
+ * nothing.
+ * Passes: test (keymap_test_kernel, unchanged: per input record the start and length of its member's list); scan
+ * (the uint32 scan of the tile counts, the compaction to kept rows, a 64-bit scan over the kept rows whose grid is
+ * sized from n_rec and which reads the kept count on the device); emit (lane = output row: a wave finds the kept row
+ * of its first output by one binary search and each lane its own within the next 64 kept rows in 6 cross-lane
+ * steps, so a wave's work is bounded by its 64 outputs).  Host waits: one, for T and n_kept together (a second one
+ * after the emit only while profiling is on, to read its duration). */
+typedef struct cbx_keymap_rows_info {
+    int64_t n_indexed_rows;     /* row_start[n_values] */
+    int64_t n_short, n_lds, n_global;   /* members each sort path took */
+    int32_t has_rows;
+    int32_t short_max, lds_max; /* the two boundaries: longest segment of the lane path / of the LDS path */
+    float index_ms;             /* all passes, HIP events while cbx_plan_set_profiling(source_plan) is on */
+} cbx_keymap_rows_info;
+
+typedef struct cbx_expand_info {
+    int64_t n_kept, n_out;
+    int64_t max_fanout;         /* the largest c(r) */
+    int64_t emit_grid;          /* workgroups of the emit pass (0: not launched) */
+    int32_t outputs_per_workgroup;
+    int32_t host_waits;
+} cbx_expand_info;
+
+int cbx_key_map_index_rows(cbx_key_map* map, cbx_plan* source_plan, const cbx_group_by* source_keys, const uint8_t* d_data,
+                           int64_t n_bytes, const cbx_selection* in, const int64_t* d_rec_off, const int32_t* d_rec_len,
+                           int64_t n_rec, int32_t rec_stride, int32_t start_offset, const cbx_filter* source_filter,
+                           int32_t max_workgroups, void* stream, cbx_keymap_rows_info* info /* may be NULL */);
+
+/* Host code only, no GPU work. */
+int cbx_key_map_rows_info(const cbx_key_map* map, cbx_keymap_rows_info* out);
+
+/* The lists as device pointers (row_start: n_values + 1 entries), valid until cbx_key_map_destroy; NULLs before the
+ * lists exist and for an empty map. */
+int cbx_key_map_rows(const cbx_key_map* map, const int64_t** d_row_start, const int64_t** d_rows);
+
+int cbx_join_records_expand(cbx_plan* plan, const uint8_t* d_data, int64_t n_bytes, const cbx_selection* in,
+                            const int64_t* d_rec_off, const int32_t* d_rec_len, int64_t n_rec, int32_t rec_stride,
+                            int32_t start_offset, int64_t first_record_id, const cbx_filter* filter,
+                            const cbx_key_set* const* sets, const int32_t* negate, int32_t n_sets, const cbx_key_map* map,
+                            int32_t join_type, cbx_selection* out, int64_t out_capacity, int64_t* n_out, int64_t* n_kept,
+                            int64_t* d_match, int64_t* d_fact_row /* may be NULL */, void* stream);
+
+/* How the plan's last cbx_join_records_expand call ran (host code only). */
+int cbx_join_expand_info(cbx_plan* plan, cbx_expand_info* out);
+
+/* Durations in ms of the plan's last cbx_join_records_expand call: test, scan (both scans and the compaction), emit,
+ * measured with HIP events while cbx_plan_set_profiling is on. */
+int cbx_join_expand_pass_times(cbx_plan* plan, float* test_ms, float* scan_ms, float* emit_ms);
+
 /* ---- the record walk with data-dependent offsets ----
  *
  * Layouts the static-offset tables above cannot express run through a per-record walk of the
